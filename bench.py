@@ -2,6 +2,7 @@
 """bench.py -- rzip-stage throughput of libmrzgpu on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload tar|rep64k] [--gib G] [--mode streams|window]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the rzip stage (mrz_rzip_chunk: front end -> sequencer ->
 record encoder, + CRC-32) over one chunk that is already resident in HBM.  The
@@ -18,15 +19,23 @@ stream on its own GPU (chunks / files are independent units of the reference: N
 scan, tags sent to rank 0 over RCCL, exact matcher on rank 0 (shard.rzip_chunk_window);
 strong scaling of a front end whose back end (the matcher) does not shard.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description):
-value = whole-job GiB/s of input consumed; roofline = algorithmic bytes
+Prints ONE JSON line on rank 0: value = whole-job GiB/s of input consumed,
+ms_per_step = wall time of one timed step; roofline = algorithmic bytes
 (N + literal bytes + stream-0 bytes) over the measured time of the
-dominant kernel (the sequencer), against the 8 TB/s HBM peak; cpu_baseline = the
-oracle (bit-exact C restatement of the reference's single-threaded rzip stage)
-timed on a bounded prefix of the same stream on this host, 8-byte and byte-wise
-match extension, and checked against a GPU run of the same prefix; shapes = the
-other workload shapes (text, noise, tar mix) on GPU and oracle, measured once,
-outside the timed region.
+dominant kernel (the sequencer) in the timed steps, against the 8 TB/s HBM peak.
+A plain run does only that: set up, warm up, time --steps steps, print.
+
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) as
+.npy files, so that two builds can be compared output for output: the inputs are
+seeded, identical from run to run with the same arguments.
+
+--full adds what the headline does not need, all outside the timed region: the
+GPU decode of the result back to the input (verify), the LZ4 gate over its
+stream blocks, cpu_baseline = the oracle (bit-exact C restatement of the
+reference's single-threaded rzip stage) timed on a bounded prefix of the same
+stream on this host, 8-byte and byte-wise match extension, and checked against
+a GPU run of the same prefix; shapes = the other workload shapes (text, noise,
+tar mix) on GPU and oracle, measured once.
 """
 import argparse
 import hashlib
@@ -98,6 +107,59 @@ def pmc_traffic():
         return None
 
 
+RESULT_FIELDS = ("s0_len", "s1_len", "crc32", "inserts", "literals", "literal_bytes", "matches", "match_bytes", "tag_hits",
+                 "tag_misses", "min_mask", "hash_count", "n_events", "victim_round")
+SAMPLE_RUN = 4096      # bytes per sampled run of a stream
+SAMPLE_RUNS = 1024     # runs per stream: at most 4 MiB of it, 16 MiB as float32
+SUM_BLOCKS = 1 << 16   # contiguous blocks per stream whose byte sums are written
+
+
+def dump_outputs(ctx, res, out_dir, seed=0):
+    """What mrz_rzip_chunk returned in the last step, as .npy files in out_dir (about 33 MiB at most):
+      result.npy          float64, the ChunkResult scalars and the ctx's victim_round in RESULT_FIELDS order
+      s{0,1}_sample.npy   float32, the stream's bytes: all of it up to SAMPLE_RUN * SAMPLE_RUNS bytes, else SAMPLE_RUNS
+                          runs of SAMPLE_RUN bytes at offsets drawn from a generator seeded with `seed`, in offset order
+      s{0,1}_block_sums.npy  float64, the byte sums of up to SUM_BLOCKS equal contiguous blocks covering the whole stream
+    The streams are read on the device (they stay where the step left them: d_s0 / d_s1)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    st = res.stats
+    vals = [res.s0_len, res.s1_len, res.crc32, st.inserts, st.literals, st.literal_bytes, st.matches, st.match_bytes,
+            st.tag_hits, st.tag_misses, res.min_mask, res.hash_count, res.n_events, ctx.victim_round]
+    np.save(os.path.join(out_dir, "result.npy"), np.array(vals, dtype=np.float64))
+    dev = torch.device("cuda", ctx.device)
+    for name, ptr, n in (("s0", res.d_s0 or 0, res.s0_len), ("s1", res.d_s1 or 0, res.s1_len)):
+        torch.cuda.synchronize()
+        if n <= SAMPLE_RUN * SAMPLE_RUNS:
+            offs = np.array([0], dtype=np.int64)
+            run = n
+        else:
+            rng = np.random.default_rng(seed)
+            offs = np.sort(rng.integers(0, n - SAMPLE_RUN + 1, size=SAMPLE_RUNS, dtype=np.int64))
+            run = SAMPLE_RUN
+        sample = torch.empty(max(len(offs) * run, 1), dtype=torch.uint8, device=dev)
+        for i, o in enumerate(offs):
+            ctx.copy_to(sample.data_ptr() + i * run, (ptr + int(o), run))
+        np.save(os.path.join(out_dir, f"{name}_sample.npy"),
+                sample[:len(offs) * run].cpu().numpy().astype(np.float32))
+        blk = max(1, -(-n // SUM_BLOCKS))
+        piece = blk * max(1, (1 << 30) // blk)  # whole blocks per staged piece
+        stage = torch.empty(min(piece, -(-n // blk) * blk), dtype=torch.uint8, device=dev)
+        sums = []
+        for a in range(0, n, piece):
+            m = min(piece, n - a)
+            torch.cuda.synchronize()
+            ctx.copy_to(stage.data_ptr(), (ptr + a, m))
+            k = -(-m // blk) * blk
+            stage[m:k].zero_()
+            sums.append(stage[:k].view(-1, blk).sum(dim=1, dtype=torch.int64))
+        sums = torch.cat(sums).cpu().numpy() if sums else np.zeros(0, dtype=np.int64)
+        np.save(os.path.join(out_dir, f"{name}_block_sums.npy"), sums.astype(np.float64))
+        del sample, stage
+    torch.cuda.synchronize()
+
+
 def shape_line(ctx, name, data, oracle_sample=None):
     """One workload shape: GPU GiB/s (one chunk, profiling events on), oracle GiB/s on the same bytes (or on a
     prefix of them), the roofline fraction recomputed the same way as for the headline."""
@@ -136,16 +198,24 @@ def main():
                          "configs[1] (10 GiB text with 64 KiB-period repeats)")
     ap.add_argument("--gib", type=float, default=0.0, help="chunk size per GPU in GiB (default: 64 for tar, 10 for rep64k)")
     ap.add_argument("--level", type=int, default=7)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extras: decode of the result, LZ4 gate, split, cpu_baseline, shapes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-sample-gib", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the other workload shapes (text, noise, tar mix)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed GPU decode of the result")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-shapes", action="store_true",
+                    help="with --full: skip the other workload shapes (text, noise, tar mix)")
+    ap.add_argument("--no-verify", action="store_true",
+                    help="with --full: skip the untimed GPU decode of the result (and the LZ4 gate)")
     ap.add_argument("--mode", default="streams", choices=["streams", "window"],
                     help="streams: one independent stream per GPU (weak scaling); window: ONE window range-sharded over "
                          "the GPUs, matcher on rank 0 (strong scaling of the front end)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the default) or gloo (rehearsal of the "
                     "multi-process path with several ranks on one GPU: ranks wrap around the visible devices)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import modern_rzip_amd as m
@@ -223,10 +293,12 @@ def main():
         tt = torch.tensor([dt], device=dev if args.dist_backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, res, args.dump_outputs)
 
     # untimed self-check on every rank: the streams of the last step decode back to the input (GPU runzip)
     verify = None
-    if not args.no_verify and res is not None:
+    if args.full and not args.no_verify and res is not None:
         back = torch.empty(n, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize()
         v0 = time.perf_counter()
@@ -276,7 +348,7 @@ def main():
         }
         if verify:
             out["verify"] = verify
-        if args.workload == "tar" and world == 1 and not args.no_verify:
+        if args.full and args.workload == "tar" and world == 1 and not args.no_verify:
             # configs[2] is "GPU rzip + LZ4 test -> host back-end": the LZ4 compressibility gate (lz4_compresses,
             # src/stream.c:1685-1733) over the blocks the two streams of this chunk would be flushed in (128 MiB stream buffers
             # at -L7, src/stream.c:907-912), on the device, untimed -- what the gate adds to a step
@@ -289,7 +361,7 @@ def main():
             gdt = time.perf_counter() - g0
             out["lz4_gate"] = {"blocks": len(blocks), "seconds": round(gdt, 3), "skip_backend": sum(1 for v in verdicts if v == 0),
                                "note": "mrz_lz4_compresses_batch over the stream blocks of the last step, device-resident, untimed"}
-        if world == 1 and args.gib > 4.5 and args.workload == "rep64k":
+        if args.full and world == 1 and args.gib > 4.5 and args.workload == "rep64k":
             # the S2 generator repeats itself exactly after 4 GiB (period i + 65536 equals period i): the tail of the
             # chunk is ONE match.  Time the part that carries the matcher's work on its own.
             n4 = 4 * GIB
@@ -305,12 +377,12 @@ def main():
                             "tail_GiBps": round((n - n4) / GIB / max(step_s - d4, 1e-9), 2),
                             "note": "beyond 4 GiB the stream repeats itself exactly: the tail is one match"}
         base = None
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             if args.workload == "tar":
                 base = cpu_baseline(ctx, int(min(args.cpu_sample_gib, args.gib) * GIB), data=data, what="tar")
             else:
                 base = cpu_baseline(ctx, int(min(args.cpu_sample_gib, args.gib) * GIB))
-        if not args.no_shapes and world == 1:
+        if args.full and not args.no_shapes and world == 1:
             del data
             torch.cuda.empty_cache()
             shapes = []
@@ -372,6 +444,8 @@ def window_mode(args, m, workloads, lib, dist, rank, world, dev_index):
         if rank == 0:
             res = out[0]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(ctx, res, args.dump_outputs)
         dt = sum(times)
         print(json.dumps({"metric": "rzip-stage GiB/s (mrzip -n)", "value": round(total * args.steps / GIB / dt, 4),
                           "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

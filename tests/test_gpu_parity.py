@@ -549,7 +549,7 @@ def test_coresident_blake2b_and_rs_beside_rzip(gpu_lib):
 
 
 def test_rs_decoder_against_the_reference(gpu_lib):
-    """mrz_rs_decode vs the reference's own rsd32 / gather (oracle/_ref/librs_ref.so) on damaged encodings."""
+    """mrz_rs_decode vs the reference's own rsd32 / gather (recorded in tests/golden/ref_outputs.json) on damaged encodings."""
     data = _util.xorshift_noise(2 * 1823248 + 777, seed=15)  # three bursts
     with m.RzipContext(lib=gpu_lib) as ctx:
         got, rep = _parity.check_rs_decode(ctx, data, [])

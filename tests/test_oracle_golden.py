@@ -1,6 +1,7 @@
 """CPU tier: pins the oracle (oracle/liboracle.so) against the reference's golden
 vectors (tests/golden/vectors.json), standard known answers and
--- where present -- oracle/_ref (the reference's own blake2b.c compiled in place)."""
+the recorded outputs of the reference's own blake2b.c and reed-solomon.c
+(tests/golden/ref_outputs.json)."""
 import ctypes
 import hashlib
 import json
@@ -16,6 +17,8 @@ ROOT = os.path.dirname(HERE)
 
 with open(os.path.join(HERE, "golden", "vectors.json")) as f:
     GOLD = json.load(f)
+with open(os.path.join(HERE, "golden", "ref_outputs.json")) as f:
+    REF = json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -102,33 +105,16 @@ def test_blake2b_known_answers(oracle):
 
 
 def test_blake2b_against_reference_build(oracle):
-    """oracle/_ref/libblake2b_ref.so = the reference's common/blake2b.c compiled in place."""
-    ref_path = os.path.join(ROOT, "oracle", "_ref", "libblake2b_ref.so")
-    if not os.path.exists(ref_path):
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    R = ctypes.CDLL(ref_path)
-
-    class St(ctypes.Structure):
-        _fields_ = [("h", ctypes.c_uint64 * 8), ("t", ctypes.c_uint64 * 2), ("f", ctypes.c_uint64 * 2),
-                    ("buf", ctypes.c_uint8 * 128), ("buflen", ctypes.c_size_t), ("outlen", ctypes.c_size_t),
-                    ("last_node", ctypes.c_uint8)]
-
-    def ref(pieces, outlen=64):
-        s = St()
-        R.blake2b_init(ctypes.byref(s), ctypes.c_size_t(outlen))
-        for p in pieces:
-            R.blake2b_update(ctypes.byref(s), p, ctypes.c_size_t(len(p)))
-        out = ctypes.create_string_buffer(64)
-        R.blake2b_final(ctypes.byref(s), out, ctypes.c_size_t(outlen))
-        return out.raw[:outlen]
-
-    for n in (0, 5, 128, 129, 223, 223 * 7, 10000):
-        d = _util.xorshift_noise(n, seed=3 * n + 1)
-        assert oracle.blake2b(d) == ref([d])
+    """The reference's common/blake2b.c (outputs recorded from oracle/_ref/libblake2b_ref.so by
+    tests/golden/make_ref_golden.py)."""
+    from tests.golden import make_ref_golden
+    for n, d in make_ref_golden.blake2b_cases():
+        want = REF["blake2b"][str(n)]
+        assert oracle.blake2b(d) == bytes.fromhex(want["whole_64"])
         # rs-mrzip style: 223-byte rows (rs-mrzip/rs-mrzip.c:132-138)
         rows = [d[i:i + 223] for i in range(0, len(d), 223)]
-        assert oracle.blake2b(d, pieces=rows) == ref(rows)
-        assert oracle.blake2b(d, 32) == ref([d], 32)
+        assert oracle.blake2b(d, pieces=rows) == bytes.fromhex(want["rows_64"])
+        assert oracle.blake2b(d, 32) == bytes.fromhex(want["whole_32"])
 
 
 def test_lz4_golden_sizes(oracle):
@@ -200,30 +186,18 @@ def test_multi_chunk_roundtrip_and_victim_round(oracle):
 
 
 def test_rs_encoder_against_reference_build(oracle):
-    """oracle/_ref/librs_ref.so = the reference's rs-mrzip/reed-solomon.c compiled in place:
-    rse32 (parity, :115-141) and scatter (interleave, :311-321)."""
-    ref_path = os.path.join(ROOT, "oracle", "_ref", "librs_ref.so")
-    if not os.path.exists(ref_path):
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    R = ctypes.CDLL(ref_path)
+    """The reference's rs-mrzip/reed-solomon.c (outputs recorded from oracle/_ref/librs_ref.so by
+    tests/golden/make_ref_golden.py): rse32 (parity, :115-141) and scatter (interleave, :311-321)."""
     for trial in range(64):
         row = bytes(223) if trial == 0 else _util.xorshift_noise(223, seed=trial)
-        buf = (ctypes.c_uint8 * 255)(*row, *([0] * 32))
-        R.rse32(buf, ctypes.byref(buf, 223))
-        assert bytes(buf)[:223] == row and bytes(buf)[223:] == oracle.rs_parity(row)
+        assert oracle.rs_parity(row) == bytes.fromhex(REF["rse32_parity"][trial])
     # one whole burst through the reference's rse32 + scatter == the oracle's encoder body
     rows, k, n = 8176, 223, 255
     data = _util.xorshift_noise(rows * k - 1000, seed=9)
-    ec = (ctypes.c_uint8 * (rows * n))()
     padded = data + bytes(1000)
-    for r in range(rows):
-        ctypes.memmove(ctypes.byref(ec, r * n), padded[r * k:(r + 1) * k], k)
-        R.rse32(ctypes.byref(ec, r * n), ctypes.byref(ec, r * n + k))
-    tr = (ctypes.c_uint8 * (rows * n))()
-    R.scatter(ec, tr, rows, n)
     enc = oracle.rs_encode(data)
     assert len(enc) == rows * n + 68
-    assert enc[: rows * n] == bytes(tr)
+    assert hashlib.sha256(enc[: rows * n]).hexdigest() == REF["scatter_sha256"]
     assert enc[rows * n: rows * n + 64] == hashlib.blake2b(padded).digest()
     ki, kj = divmod(len(data), k)
     assert enc[-4:] == bytes([ki & 255, ki >> 8, kj & 255, kj >> 8])

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_r03
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/bench_stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-shapes > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $O/bench_stats -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-shapes > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 python3 $R/tools/pmc_summary.py stats $O/bench_tar64_kernel_stats.csv $O/bench_stats > $O/bench_stats_top.txt
 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "mrz_.*" -d $O/pmc_fetch -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-shapes --no-verify > $O/pmc_fetch.json 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "mrz_.*" -d $O/pmc_write -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-shapes --no-verify > $O/pmc_write.json 2> $O/pmc_write.err
