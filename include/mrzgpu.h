@@ -32,7 +32,8 @@ enum {
     MRZ_E_NODEVICE = -2, /* no HIP device / HIP runtime failure at open */
     MRZ_E_NOMEM = -3,    /* device or host allocation failed */
     MRZ_E_HIP = -4,      /* HIP runtime error during a call (see mrz_last_hip_error) */
-    MRZ_E_OVERFLOW = -5, /* internal capacity exceeded (should not happen) */
+    MRZ_E_OVERFLOW = -5, /* internal consistency check failed (should not happen; the match list is drained in pieces,
+                          * never overflowed) */
     MRZ_E_STATE = -6,    /* call order violated (e.g. fetch before a chunk ran) */
     MRZ_E_CORRUPT = -7,  /* runzip: invalid record stream / archive (the reference fatal()s "corrupt archive") */
     MRZ_E_UNSUPPORTED = -8 /* runzip: block type other than CTYPE_NONE (back-end codecs are host code) */
@@ -81,7 +82,8 @@ typedef struct {
     int32_t n_segments; /* sequencer launches (segments an emitted match has covered are not launched) */
     int32_t n_narrow;   /* ... of which ran on the narrow engine (mrz_seq_narrow.hip) */
     int32_t n_deep;     /* ... and on the deep engine (mrz_seq_deep.hip); the rest on the wide engine */
-    int32_t reserved;
+    int32_t n_event_flushes; /* pieces of the match list encoded before the final one (0 unless the chunk could emit
+                              * more matches than the list holds: mrz_set_event_capacity) */
 } mrz_timings;
 
 /* ---- context ----------------------------------------------------------- */
@@ -125,8 +127,18 @@ typedef struct {
 } mrz_match;
 typedef int (*mrz_progress_fn)(void *user, int64_t n_events, int64_t last_match, int chunk_done);
 int mrz_set_progress(mrz_ctx *ctx, mrz_progress_fn fn, void *user);
-/* copies matches [first, first + count) of the chunk in flight (or of the last chunk) to host memory */
+/* copies matches [first, first + count) of the chunk in flight (or of the last chunk) to host memory.  Indices count
+ * from the chunk's first match.  When the chunk emits more matches than the match list holds (mrz_set_event_capacity),
+ * the list is encoded into the streams in pieces and the matches of a piece leave it: a range that starts before the
+ * list's first match then fails with MRZ_E_STATE.  A piece leaves the list only after `fn` has been called for every
+ * match of it, so a consumer that fetches inside `fn` (as mrz_rzip_pipeline does) sees every match. */
 int mrz_fetch_events(mrz_ctx *ctx, int64_t first, int64_t count, mrz_match *host_dst);
+/* Entries of the device match list (24 B each) from the next chunk on: 1024 .. 2^31 entries; 0 or negative = the
+ * default, min(chunk / 31 + 2, 2^28) -- room for every match a chunk of up to 8.3 GB can emit.  A chunk that can emit
+ * more is not refused: whenever the list runs short of room, the matches it holds are encoded into the two streams and
+ * the list is reused (mrz_timings.n_event_flushes counts these pieces; the streams are the same bytes).  The
+ * MRZ_EVENT_CAPACITY environment variable, read by mrz_open, sets a ctx's initial value. */
+int mrz_set_event_capacity(mrz_ctx *ctx, int64_t entries);
 
 /* ---- the front end's candidate list; one window over several GPUs (second row; BASELINE configs[3]) ----
  * The tag of every position (single_full_tag / next_tag, src/rzip.c:330-358) is computed by a parallel front end, and

@@ -31,7 +31,7 @@ class ChunkResult(ctypes.Structure):
 class Timings(ctypes.Structure):
     _fields_ = [("tagscan_ms", ctypes.c_float), ("sequencer_ms", ctypes.c_float), ("encode_ms", ctypes.c_float),
                 ("crc_ms", ctypes.c_float), ("total_ms", ctypes.c_float), ("n_segments", ctypes.c_int32),
-                ("n_narrow", ctypes.c_int32), ("n_deep", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("n_narrow", ctypes.c_int32), ("n_deep", ctypes.c_int32), ("n_event_flushes", ctypes.c_int32)]
 
 
 # mrz_cand_provider_fn (include/mrzgpu.h)
@@ -104,6 +104,8 @@ def load_library(path=None):
         lib.mrz_set_cand_provider.argtypes = [vp, CAND_FN, vp]
         lib.mrz_set_segment_positions.argtypes = [vp, i64]
         lib.mrz_set_candidate_capacity.argtypes = [vp, i64]
+    if hasattr(lib, "mrz_set_event_capacity"):
+        lib.mrz_set_event_capacity.argtypes = [vp, i64]
         lib.mrz_set_xcd.argtypes = [vp, ci]
         lib.mrz_copy_to_device.argtypes = [vp, vp, vp, i64]
         lib.mrz_copy_device.argtypes = [vp, vp, vp, i64]
@@ -280,6 +282,11 @@ class RzipContext:
 
     def set_candidate_capacity(self, entries):
         _check(self.lib, self.lib.mrz_set_candidate_capacity(self.ctx, entries), self.ctx)
+
+    def set_event_capacity(self, entries):
+        """mrz_set_event_capacity: entries of the device match list from the next chunk on (1024 .. 2^31; <= 0: the
+        default).  A chunk that can emit more matches is encoded in pieces (timings().n_event_flushes)."""
+        _check(self.lib, self.lib.mrz_set_event_capacity(self.ctx, entries), self.ctx)
 
     def set_xcd(self, xcd):
         _check(self.lib, self.lib.mrz_set_xcd(self.ctx, xcd), self.ctx)

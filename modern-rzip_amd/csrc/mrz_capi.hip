@@ -45,9 +45,13 @@ extern "C" int mrz_abi_version(void) { return MRZ_ABI_VERSION; }
 // Room for the emitted matches of a chunk of n bytes (24 B each).  Matches are >= 31 bytes and disjoint, so n / 31 + 2
 // always suffices -- 53 GB for a 64 GiB chunk, more than the chunk for a 256 GiB window.  Beyond MRZ_EVENT_CAP entries
 // (6.4 GB: one match per 256 bytes of a 64 GiB chunk; text emits one per ~400 bytes, the tar mix one per 500 KB) the
-// list is bounded instead; a chunk that would overflow it fails with MRZ_E_OVERFLOW (the sequencers stop at the cap).
+// list is bounded instead, and mrz_rzip_chunk encodes it in pieces whenever it runs short of room (the room rule
+// there).  mrz_set_event_capacity / MRZ_EVENT_CAPACITY set the bound by hand (MRZ_EVENT_MIN at least).
 #define MRZ_EVENT_CAP (1ll << 28)
-static int64_t mrz_event_room(int64_t n) {
+#define MRZ_EVENT_MIN 1024ll
+#define MRZ_EVENT_MAX (1ll << 31)
+static int64_t mrz_event_room(const mrz_ctx *ctx, int64_t n) {
+    if (ctx->event_cap_set > 0) return ctx->event_cap_set;
     const int64_t worst = n / MRZ_MIN_MATCH + 2;
     return worst < MRZ_EVENT_CAP ? worst : MRZ_EVENT_CAP;
 }
@@ -155,6 +159,14 @@ extern "C" int mrz_open(mrz_ctx **out, int device, int level, int64_t max_chunk)
         if (const char *d = getenv("MRZ_NARROW_MAX_BITS")) ctx->narrow_max_bits = atoi(d);
         e = getenv("MRZ_PRINT_PROF");
         if (e) ctx->print_prof = !strcmp(e, "narrow") ? 2 : 1;
+        if (const char *c = getenv("MRZ_EVENT_CAPACITY")) {  // (as mrz_set_event_capacity; out of range: the default)
+            const long long v = atoll(c);
+            if (v >= MRZ_EVENT_MIN && v <= MRZ_EVENT_MAX)
+                ctx->event_cap_set = v;
+            else if (v > 0)
+                fprintf(stderr, "libmrzgpu: MRZ_EVENT_CAPACITY=%s ignored (%lld .. %lld entries)\n", c, MRZ_EVENT_MIN,
+                        MRZ_EVENT_MAX);
+        }
     }
     ctx->farm_default = mrz_sequencer_default_helpers(device);
     ctx->device = device;
@@ -223,7 +235,7 @@ extern "C" int mrz_open(mrz_ctx **out, int device, int level, int64_t max_chunk)
         if (const char *e = getenv("MRZ_DEEP_SCANNERS")) ctx->deep_scanners = atoi(e);
     }
     if (!rc && max_chunk > 0) {
-        rc = mrz_grow(ctx, &ctx->d_events, &ctx->event_cap, mrz_event_room(max_chunk));
+        rc = mrz_grow(ctx, &ctx->d_events, &ctx->event_cap, mrz_event_room(ctx, max_chunk));
         if (!rc) rc = mrz_grow(ctx, &ctx->d_crc_parts, &ctx->crc_parts_cap, mrz_crc32_parts_needed(max_chunk));
         if (!rc) rc = mrz_fe_reserve(ctx, max_chunk / MRZ_TILE + 2, max_chunk);
     }
@@ -260,11 +272,12 @@ extern "C" int mrz_set_progress(mrz_ctx *ctx, mrz_progress_fn fn, void *user) {
 extern "C" int mrz_fetch_events(mrz_ctx *ctx, int64_t first, int64_t count, mrz_match *host_dst) {
     if (!ctx || first < 0 || count < 0 || (count > 0 && !host_dst)) return MRZ_E_ARG;
     if (first + count > ctx->events_final) return MRZ_E_STATE;
+    if (first < ctx->ev_base) return MRZ_E_STATE;  // encoded and dropped from the list (the progress hook saw them)
     if (!count) return MRZ_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->copy_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     static_assert(sizeof(mrz_match) == sizeof(mrz_event), "mrz_match mirrors mrz_event");
-    HIPCHK(ctx, hipMemcpyAsync(host_dst, ctx->d_events + first, (size_t)count * sizeof(mrz_event), hipMemcpyDeviceToHost,
+    HIPCHK(ctx, hipMemcpyAsync(host_dst, ctx->d_events + (first - ctx->ev_base), (size_t)count * sizeof(mrz_event), hipMemcpyDeviceToHost,
                                ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     return MRZ_OK;
@@ -304,6 +317,12 @@ extern "C" int mrz_set_segment_positions(mrz_ctx *ctx, int64_t positions) {
 extern "C" int mrz_set_candidate_capacity(mrz_ctx *ctx, int64_t entries) {
     if (!ctx || entries < MRZ_TILE || entries > (1ll << 30)) return MRZ_E_ARG;
     ctx->cand_cap = entries;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_set_event_capacity(mrz_ctx *ctx, int64_t entries) {
+    if (!ctx || (entries > 0 && entries < MRZ_EVENT_MIN) || entries > MRZ_EVENT_MAX) return MRZ_E_ARG;
+    ctx->event_cap_set = entries > 0 ? entries : 0;
     return MRZ_OK;
 }
 
@@ -477,8 +496,12 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     const uint8_t *d_buf = nullptr;
     int rc = mrz_stage_input(ctx, chunk, n, where, &d_buf);
     if (rc) return rc;
-    rc = mrz_grow(ctx, &ctx->d_events, &ctx->event_cap, mrz_event_room(n));
+    rc = mrz_grow(ctx, &ctx->d_events, &ctx->event_cap, mrz_event_room(ctx, n));
     if (rc) return rc;
+    // entries the sequencers may fill (by default all the list holds); `bounded`: fewer than the chunk could emit, so the
+    // list is drained in pieces (the room rule below)
+    const int64_t ev_cap = ctx->event_cap_set > 0 ? ctx->event_cap_set : ctx->event_cap;
+    const bool bounded = ev_cap < n / MRZ_MIN_MATCH + 2;
     rc = mrz_grow(ctx, &ctx->d_crc_parts, &ctx->crc_parts_cap, mrz_crc32_parts_needed(n));
     if (rc) return rc;
     const int64_t end = n - MRZ_MIN_MATCH;  // last position that is looked up (src/rzip.c:544)
@@ -530,7 +553,7 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     hs.victim_round = *victim_round;
     hs.max_chain = ctx->max_chain;
     hs.slot_mask = ctx->nslots - 1;
-    hs.event_cap = ctx->event_cap;
+    hs.event_cap = ev_cap;
     hs.finished = end > 0 ? 0 : 1;
     hipError_t herr = hipSuccess;
     int64_t E = 0;
@@ -559,6 +582,7 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     // snapshot of the matcher state in a ring of pinned host slots (ONE copy per launch: position, masks, progress and
     // the `finished` flag belong together); the host reads a slot once the launch's event has completed.
     ctx->events_final = 0;
+    ctx->ev_base = 0;
     const size_t snap_bytes = offsetof(mrz_seq_state, prof);
     hipEvent_t seg_ev[MRZ_SEG_AHEAD];
     int n_seg_ev = 0;
@@ -571,6 +595,7 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     int64_t known_next = 0;              // where the pass after the last retired launch begins, as far as the host knows
     int64_t known_mask = hs.min_mask, known_p = 0;
     int64_t hint_pos = 0, hint_matched = 0;
+    int64_t known_events = 0, known_last = 0;  // matches emitted by the last retired launch, and where the last one ended
     bool finished = end <= 0;
     // a launch whose event has completed: its snapshot is final
     auto retire = [&]() {
@@ -578,6 +603,8 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
         retired++;
         known_p = sn->p;
         known_mask = sn->min_mask;
+        known_events = sn->n_events;
+        known_last = sn->last_match;
         if (!ctx->cand_fn)
             known_next = sn->scan_next;
         else if (sn->seg_end > sn->seg_start && sn->scan_next < sn->seg_end)
@@ -593,6 +620,53 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
         }
         if (sn->finished || sn->error) finished = true;
     };
+    // ---- pieces: the matches [ctx->ev_base, upto) are encoded into the streams behind what is there and leave the list
+    // (nothing is in flight: the stream holds only finished launches, and retire() has shown all of them to the hook)
+    int64_t base0 = 0, base1 = 0, lit_from = 0, n_flushes = 0;  // stream bytes so far; first literal of the next piece
+    auto encode_piece = [&](int64_t upto, int final_piece) {
+        const int64_t Ep = upto - ctx->ev_base;
+        const int64_t nblocks = (Ep + 1 + 255) / 256;
+        int r = mrz_grow(ctx, &ctx->d_block_s0, &ctx->block_cap, nblocks);
+        if (!r) r = mrz_grow(ctx, &ctx->d_block_s1, &ctx->block1_cap, nblocks);
+        if (!r) r = mrz_grow(ctx, &ctx->d_lit_off, &ctx->lit_off_cap, Ep + 2);
+        if (r) return r;
+        PROF_BEGIN(2);
+        STEP(mrz_launch_enc_size(s, ctx->d_events, Ep, final_piece, lit_from, n, chunk_bytes, ctx->d_block_s0,
+                                 ctx->d_block_s1, base0, base1, ctx->d_totals));
+        STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+        STEP(hipStreamSynchronize(s));
+        if (herr == hipSuccess) {
+            // (a chunk without drains: the streams of the last chunk are not kept)
+            if (!base0) r = mrz_grow(ctx, &ctx->d_s0, &ctx->s0_cap, tot.s0_len + 7 + 16);
+            else r = mrz_grow_keep(ctx, &ctx->d_s0, &ctx->s0_cap, base0 + tot.s0_len + 7 + 16, base0);
+            if (!r && !base1) r = mrz_grow(ctx, &ctx->d_s1, &ctx->s1_cap, tot.s1_len + 16);
+            else if (!r) r = mrz_grow_keep(ctx, &ctx->d_s1, &ctx->s1_cap, base1 + tot.s1_len + 16, base1);
+        }
+        if (herr == hipSuccess && !r) {
+            STEP(mrz_launch_enc_write(s, d_buf, ctx->d_events, Ep, final_piece, lit_from, n, chunk_bytes, ctx->d_block_s0,
+                                      ctx->d_block_s1, ctx->d_s0, ctx->d_s1, base1, tot.s1_len, ctx->d_lit_off,
+                                      ctx->d_totals, crc));
+            STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+        }
+        PROF_END();
+        return r;
+    };
+    auto drain = [&]() {
+        const int r = encode_piece(known_events, 0);
+        if (r || herr != hipSuccess) return r;
+        ctx->ev_base = known_events;
+        STEP(hipMemcpyAsync(&ctx->d_state->ev_base, &ctx->ev_base, sizeof(int64_t), hipMemcpyHostToDevice, s));
+        STEP(hipStreamSynchronize(s));
+        base0 += tot.s0_len;
+        base1 += tot.s1_len;
+        lit_from = known_last;  // (the end of the piece's last match)
+        n_flushes++;
+        return 0;
+    };
+    // the span of one pass when the list is bounded: half the list's worth of positions, so that a drained list always
+    // has room for the next pass (the room rule)
+    int64_t pass_cap = MRZ_MIN_MATCH * (ev_cap / 2) / MRZ_TILE * MRZ_TILE;
+    if (pass_cap < MRZ_TILE) pass_cap = MRZ_TILE;
     while (!finished && herr == hipSuccess && !rc) {
         // whatever has completed meanwhile (the engine choice and the span below want the matcher's latest news)
         while (retired < launched && !finished && !rc && hipEventQuery(seg_ev[retired % MRZ_SEG_AHEAD]) == hipSuccess) retire();
@@ -616,9 +690,59 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
         }
         // ---- one more segment
         int64_t span = mrz_span_for_mask(ctx, known_mask);
+        if (bounded && span > pass_cap) span = pass_cap;
         int64_t max_tiles = span / MRZ_TILE;
         if (max_tiles > ctx->fe_tiles_cap) max_tiles = ctx->fe_tiles_cap;
         span = max_tiles * MRZ_TILE;
+        if (bounded) {
+            // The room rule: queue a pass only if the list can take every match the launches after the latest retired
+            // one (snapshot S: n_events_S matches, matcher at v = known_p) can emit.  Every position <= v has been looked
+            // at under the mask of S (a launch that used up its list leaves p at its pass's last position, lim; one that
+            // ended early, as on the wide-to-deep hand-over, leaves its real p and scan_next goes back to p's tile), and
+            // masks only tighten, so the matches emitted after S are
+            //   - the match pending in S (cur_len > 0), or a longer one that replaces it, and one match found beyond v
+            //     whose backward extension reaches before it: 2;
+            //   - matches that start at or after v: disjoint, >= 31 bytes, each emitted at a candidate -- a position of
+            //     one of the queued passes, so at or before F, the last position of the furthest one (clamped to end)
+            //     -- and starting no later than that candidate (src/rzip.c:586-599: cur_p <= p, and p returns to
+            //     last_match): at most 1 + (F - v) / 31.
+            // F is estimated from where the pass after S begins (scan_next, or the tile of v + 1 when an emitted match
+            // has carried the matcher further) plus the spans of the passes in flight.  A pass begins later than that
+            // only where a match emitted by the launch before carried p beyond its end: the positions skipped lie
+            // inside that one match, so each launch adds at most one match to the estimate -- counted below as one per
+            // launch after S.  (Passes cut short by a full candidate list, or scanned again after a hand-over, only
+            // end earlier.)  Provider mode: known_next is already where the furthest queued stretch ends.
+            const int64_t pt = (known_p + 1) / MRZ_TILE * MRZ_TILE;
+            int64_t from = known_next > pt ? known_next : pt;
+            for (int64_t k = retired; k < launched; k++) from += span_of[k % MRZ_SEG_AHEAD];
+            const int64_t fixed = known_events - ctx->ev_base + 2 + 1 + (launched - retired + 1);
+            int64_t F = from + span - 1;
+            if (F > end) F = end;
+            if (fixed + (F - known_p) / MRZ_MIN_MATCH > ev_cap) {
+                if (launched > retired) {  // wait for the oldest launch: S moves on
+                    STEP(hipEventSynchronize(seg_ev[retired % MRZ_SEG_AHEAD]));
+                    if (herr != hipSuccess) break;
+                    retire();
+                    continue;
+                }
+                if (known_events > ctx->ev_base) {  // nothing in flight: encode what the list holds and empty it
+                    rc = drain();
+                    continue;
+                }
+                // Nothing in flight and nothing to drain: shorten the pass to what fits.  No stall: here v + 1 >= the
+                // start of the pass after S less one pass at most (v is lim, or p behind a match, or p with scan_next
+                // taken back to its tile -- from is v + 1 or a tile start <= v + 1, or at most pass_cap beyond), so
+                // the room left is 31 x (ev_cap - 4) + 30 - pass_cap >= 31 x ev_cap / 2 - 94 positions: more than one
+                // tile for every capacity >= MRZ_EVENT_MIN.
+                const int64_t fit = (ev_cap - fixed) * MRZ_MIN_MATCH + MRZ_MIN_MATCH - 1 - (from - 1 - known_p);
+                if (fit < MRZ_TILE) {  // (cannot happen, see above)
+                    rc = MRZ_E_OVERFLOW;
+                    break;
+                }
+                if (span > fit) span = fit / MRZ_TILE * MRZ_TILE;
+                max_tiles = span / MRZ_TILE;
+            }
+        }
         PROF_BEGIN(0);
         if (ctx->cand_fn) {
             // window sharding: the stretch's owner scans it (with the mask this rank has last heard of); the host drives
@@ -714,28 +838,9 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
         }
     }
 
-    // record encoding
+    // record encoding: the last piece (the whole chunk unless the list has been drained)
     if (herr == hipSuccess && !rc) {
-        const int64_t nblocks = (E + 1 + 255) / 256;
-        rc = mrz_grow(ctx, &ctx->d_block_s0, &ctx->block_cap, nblocks);
-        if (!rc) rc = mrz_grow(ctx, &ctx->d_block_s1, &ctx->block1_cap, nblocks);
-        if (!rc) rc = mrz_grow(ctx, &ctx->d_lit_off, &ctx->lit_off_cap, E + 2);
-    }
-    if (herr == hipSuccess && !rc) {
-        PROF_BEGIN(2);
-        STEP(mrz_launch_enc_size(s, ctx->d_events, E, n, chunk_bytes, ctx->d_block_s0, ctx->d_block_s1, ctx->d_totals));
-        STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-        STEP(hipStreamSynchronize(s));
-        if (herr == hipSuccess) {
-            rc = mrz_grow(ctx, &ctx->d_s0, &ctx->s0_cap, tot.s0_len + 7 + 16);
-            if (!rc) rc = mrz_grow(ctx, &ctx->d_s1, &ctx->s1_cap, tot.s1_len + 16);
-        }
-        if (herr == hipSuccess && !rc) {
-            STEP(mrz_launch_enc_write(s, d_buf, ctx->d_events, E, n, chunk_bytes, ctx->d_block_s0, ctx->d_block_s1,
-                                      ctx->d_s0, ctx->d_s1, tot.s1_len, ctx->d_lit_off, ctx->d_totals, crc));
-            STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-        }
-        PROF_END();
+        rc = encode_piece(E, 1);
         if (ctx->profiling) hipEventRecord(ev_end, s);
         STEP(hipStreamSynchronize(s));
     }
@@ -743,6 +848,7 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     ctx->timings.n_segments = (int32_t)launched;
     ctx->timings.n_narrow = (int32_t)n_narrow;
     ctx->timings.n_deep = (int32_t)n_deep;
+    ctx->timings.n_event_flushes = (int32_t)n_flushes;
     if (ctx->profiling) {
         hipStreamSynchronize(s);
         for (int i = 0; i < nev; i++) {
@@ -772,8 +878,8 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     if (rc) return rc;
 
     *victim_round = hs.victim_round;
-    ctx->s0_len = tot.s0_len + 7;
-    ctx->s1_len = tot.s1_len;
+    ctx->s0_len = base0 + tot.s0_len + 7;
+    ctx->s1_len = base1 + tot.s1_len;
     ctx->have_chunk = 1;
     res->s0_len = ctx->s0_len;
     res->s1_len = ctx->s1_len;

@@ -39,8 +39,9 @@ struct mrz_seq_state {
     int64_t victim_round; // static victim_round of insert_hash
     int64_t max_chain;    // level->max_chain_len
     int64_t slot_mask;    // (1 << hash_bits) - 1
-    int64_t n_events;
-    int64_t event_cap;
+    int64_t n_events;     // matches emitted so far (absolute: counts the ones already encoded and dropped from the list)
+    int64_t event_cap;    // entries of the event list
+    int64_t ev_base;      // absolute index of the list's first entry: match k is at events[k - ev_base]
     int64_t inserts, tag_hits, tag_misses;  // stats
     int32_t finished;     // main loop has reached `end`
     int32_t error;        // nonzero: event list overflow etc.

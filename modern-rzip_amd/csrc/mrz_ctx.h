@@ -45,6 +45,8 @@ struct mrz_ctx {
     int xcd;               // block index mod 8 of this ctx's sequencer workgroups (concurrent ctxs: one XCD each)
     mrz_event *d_events;
     int64_t event_cap;
+    int64_t event_cap_set;  // entries of the list from mrz_set_event_capacity / MRZ_EVENT_CAPACITY; 0 = by chunk size
+    int64_t ev_base;        // absolute index of d_events[0] in the chunk in flight (> 0 once the list has been drained)
     int64_t *d_block_s0, *d_block_s1;
     int64_t block_cap, block1_cap;
     int64_t *d_lit_off;
@@ -122,6 +124,37 @@ static inline int mrz_grow(mrz_ctx *ctx, T **ptr, int64_t *cap, int64_t want) {
     return MRZ_OK;
 }
 
+// the same, but the first `keep` elements are carried over (copied on the ctx stream): stream buffers that a later
+// piece of the chunk appends to.  Grows by half at least (pieces append a little at a time).
+template <typename T>
+static inline int mrz_grow_keep(mrz_ctx *ctx, T **ptr, int64_t *cap, int64_t want, int64_t keep) {
+    if (want <= *cap && *ptr) return MRZ_OK;
+    int64_t ask = *cap + *cap / 2 > want ? *cap + *cap / 2 : want;
+    if (ask < 16) ask = 16;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)ask * sizeof(T));
+    if (e != hipSuccess && ask > want) {
+        ask = want;
+        e = hipMalloc(&p, (size_t)ask * sizeof(T));
+    }
+    if (e != hipSuccess) {
+        ctx->last_err = e;
+        return MRZ_E_NOMEM;
+    }
+    if (*ptr) {
+        if (keep > 0) e = hipMemcpyAsync(p, *ptr, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            hipFree(p);
+            ctx->last_err = e;
+            return MRZ_E_HIP;
+        }
+        hipFree(*ptr);
+    }
+    *ptr = (T *)p;
+    *cap = ask;
+    return MRZ_OK;
+}
 
 // (re)allocates the front end's buffers for passes of up to `tiles` tiles and lists of up to `entries` candidates
 int mrz_fe_reserve(mrz_ctx *ctx, int64_t tiles, int64_t entries);

@@ -13,14 +13,22 @@
 // then every item writes its records at its own offset and the literal bytes
 // are gathered by a grid-wide copy (16 B per thread, unaligned source).
 //
+// A chunk is encoded in one or more PIECES (mrz_capi.hip drains the event list
+// when it runs short of room): a piece's matches start at ev[0], its first
+// literal run at lit0 (the end of the previous piece's last match; 0 for the
+// first), its records at offset base0 of stream 0 and its literal bytes at
+// base1 of stream 1.  Only the final piece has item E (the trailing run) and
+// the terminator; the counters in `totals` add up across pieces.  One piece
+// with lit0 = base0 = base1 = 0 is the whole chunk.
+//
 // Bound: HBM (reads <= N literal bytes once, writes them once).
 #include "mrz_device.h"
 
 #define MRZ_ENC_THREADS 256
 
-__device__ __forceinline__ void mrz_item(const mrz_event *ev, int64_t E, int64_t n, int64_t i, int64_t *lit_from,
-                                         int64_t *lit_len, int64_t *mp, int64_t *mofs, int64_t *mlen) {
-    const int64_t prev_end = i ? ev[i - 1].p + ev[i - 1].len : 0;
+__device__ __forceinline__ void mrz_item(const mrz_event *ev, int64_t E, int64_t lit0, int64_t n, int64_t i,
+                                         int64_t *lit_from, int64_t *lit_len, int64_t *mp, int64_t *mofs, int64_t *mlen) {
+    const int64_t prev_end = i ? ev[i - 1].p + ev[i - 1].len : lit0;
     *lit_from = prev_end;
     if (i < E) {
         *lit_len = ev[i].p - prev_end;
@@ -34,6 +42,9 @@ __device__ __forceinline__ void mrz_item(const mrz_event *ev, int64_t E, int64_t
 }
 
 __device__ __forceinline__ int64_t mrz_pieces(int64_t len) { return (len + 0xFFFE) / 0xFFFF; }
+
+// items of a piece of E matches: the trailing literal run (item E) belongs to the final piece only
+static inline int64_t mrz_enc_items(int64_t E, int final_piece) { return final_piece ? E + 1 : E; }
 
 // block-wide exclusive scan of two int64 values; returns block totals
 __device__ static void mrz_block_scan2(int64_t &a, int64_t &b, int64_t &ta, int64_t &tb) {
@@ -63,14 +74,14 @@ __device__ static void mrz_block_scan2(int64_t &a, int64_t &b, int64_t &ta, int6
 
 // pass 1: per-block totals of (stream-0 bytes, stream-1 bytes)
 __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_size_kernel(const mrz_event *__restrict__ ev, int64_t E,
-                                                                       int64_t n, int cb,
+                                                                       int64_t items, int64_t lit0, int64_t n, int cb,
                                                                        int64_t *__restrict__ block_s0,
                                                                        int64_t *__restrict__ block_s1) {
     const int64_t i = (int64_t)blockIdx.x * MRZ_ENC_THREADS + threadIdx.x;
     int64_t c0 = 0, c1 = 0;
-    if (i <= E) {
+    if (i < items) {
         int64_t lf, ll, mp, mo, ml;
-        mrz_item(ev, E, n, i, &lf, &ll, &mp, &mo, &ml);
+        mrz_item(ev, E, lit0, n, i, &lf, &ll, &mp, &mo, &ml);
         c0 = mrz_pieces(ll) * 3 + mrz_pieces(ml) * (3 + cb);
         c1 = ll;
     }
@@ -82,11 +93,11 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_size_kernel(const mrz
     }
 }
 
-// pass 2: one workgroup turns the block totals into exclusive offsets and
-// publishes the grand totals
+// pass 2: one workgroup turns the block totals into exclusive offsets (from the piece's base0 / base1) and
+// publishes the piece's totals
 __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_scan_kernel(int64_t *__restrict__ block_s0,
                                                                        int64_t *__restrict__ block_s1,
-                                                                       int64_t nblocks,
+                                                                       int64_t nblocks, int64_t base0, int64_t base1,
                                                                        mrz_enc_totals *__restrict__ totals) {
     int64_t run0 = 0, run1 = 0;
     for (int64_t base = 0; base < nblocks; base += MRZ_ENC_THREADS) {
@@ -95,8 +106,8 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_scan_kernel(int64_t *
         int64_t ta, tb;
         mrz_block_scan2(a, b, ta, tb);
         if (i < nblocks) {
-            block_s0[i] = run0 + a;
-            block_s1[i] = run1 + b;
+            block_s0[i] = base0 + run0 + a;
+            block_s1[i] = base1 + run1 + b;
         }
         run0 += ta;
         run1 += tb;
@@ -131,7 +142,7 @@ __device__ __forceinline__ void mrz_put_record(uint8_t *__restrict__ s0, int64_t
 
 // pass 3: records into stream 0, per-item stream-1 offsets, statistics
 __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_write_kernel(const mrz_event *__restrict__ ev, int64_t E,
-                                                                        int64_t n, int cb,
+                                                                        int64_t items, int64_t lit0, int64_t n, int cb,
                                                                         const int64_t *__restrict__ block_s0,
                                                                         const int64_t *__restrict__ block_s1,
                                                                         uint8_t *__restrict__ s0,
@@ -141,14 +152,14 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_write_kernel(const mr
     const int64_t i = (int64_t)blockIdx.x * MRZ_ENC_THREADS + threadIdx.x;
     int64_t c0 = 0, c1 = 0;
     int64_t lf = 0, ll = 0, mp = 0, mo = 0, ml = 0;
-    if (i <= E) {
-        mrz_item(ev, E, n, i, &lf, &ll, &mp, &mo, &ml);
+    if (i < items) {
+        mrz_item(ev, E, lit0, n, i, &lf, &ll, &mp, &mo, &ml);
         c0 = mrz_pieces(ll) * 3 + mrz_pieces(ml) * (3 + cb);
         c1 = ll;
     }
     int64_t ta, tb;
     mrz_block_scan2(c0, c1, ta, tb);
-    const bool live = i <= E;
+    const bool live = i < items;
     int64_t o0 = block_s0[blockIdx.x] + c0;
     const int64_t o1 = block_s1[blockIdx.x] + c1;
     if (live) lit_off[i] = o1;
@@ -198,9 +209,9 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_write_kernel(const mr
             if (v3) atomicAdd((unsigned long long *)&totals->match_bytes, (unsigned long long)v3);
         }
     }
+    if (live && i == items - 1) lit_off[items] = o1 + ll;
     if (live && i == E) {
-        // terminator literal + CRC (src/rzip.c:664-665); o0 == total s0_len here
-        lit_off[E + 1] = o1 + ll;
+        // terminator literal + CRC (src/rzip.c:664-665); o0 == total s0_len here (the final piece's last item)
         s0[o0] = 0;
         s0[o0 + 1] = 0;
         s0[o0 + 2] = 0;
@@ -211,20 +222,24 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_enc_write_kernel(const mr
     }
 }
 
-// pass 4: gather the literal bytes into stream 1 (write_sbstream, :197-211)
+// pass 4: gather the literal bytes into stream 1 (write_sbstream, :197-211).  The piece's bytes are
+// [s1_from, s1_to) of the stream; lit_off[0..items] (absolute) are its items' offsets.  Threads own 16-byte words of
+// the stream counted from s1_from rounded down to 16 (the first word of a later piece is shared with the piece before:
+// its thread writes only the bytes from s1_from on).
 __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_literal_gather_kernel(const uint8_t *__restrict__ buf,
                                                                              const mrz_event *__restrict__ ev,
-                                                                             int64_t E,
+                                                                             int64_t items, int64_t lit0,
                                                                              const int64_t *__restrict__ lit_off,
-                                                                             int64_t s1_len,
+                                                                             int64_t s1_from, int64_t s1_to,
                                                                              uint8_t *__restrict__ s1) {
     __shared__ int64_t s_lo, s_hi;
-    const int64_t blk_o = (int64_t)blockIdx.x * MRZ_ENC_THREADS * 16;
+    const int64_t blk_o = (s1_from & ~(int64_t)15) + (int64_t)blockIdx.x * MRZ_ENC_THREADS * 16;
     // narrow the item range for this block: items lo..hi cover [blk_o, blk_o + 4096)
     if (threadIdx.x < 2) {
         int64_t target = threadIdx.x == 0 ? blk_o : blk_o + (int64_t)MRZ_ENC_THREADS * 16 - 1;
-        if (target >= s1_len) target = s1_len - 1;
-        int64_t lo = 0, hi = E;  // largest i with lit_off[i] <= target
+        if (target >= s1_to) target = s1_to - 1;
+        if (target < s1_from) target = s1_from;
+        int64_t lo = 0, hi = items - 1;  // largest i with lit_off[i] <= target
         while (lo < hi) {
             const int64_t mid = (lo + hi + 1) >> 1;
             if (lit_off[mid] <= target)
@@ -239,56 +254,66 @@ __global__ __launch_bounds__(MRZ_ENC_THREADS) void mrz_literal_gather_kernel(con
     }
     __syncthreads();
     const int64_t o = blk_o + (int64_t)threadIdx.x * 16;
-    if (o >= s1_len) return;
+    if (o >= s1_to) return;
+    const int64_t w0 = o < s1_from ? s1_from : o;
     int64_t lo = s_lo, hi = s_hi;
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) >> 1;
-        if (lit_off[mid] <= o)
+        if (lit_off[mid] <= w0)
             lo = mid;
         else
             hi = mid - 1;
     }
     int64_t i = lo;
-    // skip empty runs so that lit_off[i] <= o < lit_off[i+1]
-    while (lit_off[i + 1] <= o) i++;
-    int64_t from = (i ? ev[i - 1].p + ev[i - 1].len : 0) + (o - lit_off[i]);
-    if (o + 16 <= lit_off[i + 1]) {
+    // skip empty runs so that lit_off[i] <= w0 < lit_off[i+1]
+    while (lit_off[i + 1] <= w0) i++;
+    int64_t from = (i ? ev[i - 1].p + ev[i - 1].len : lit0) + (w0 - lit_off[i]);
+    if (w0 == o && o + 16 <= lit_off[i + 1]) {
         *reinterpret_cast<uint4 *>(s1 + o) = mrz_ld16(buf + from);
         return;
     }
-    const int64_t stop = (o + 16 < s1_len) ? o + 16 : s1_len;
+    const int64_t stop = (o + 16 < s1_to) ? o + 16 : s1_to;
     int64_t run_end = lit_off[i + 1];
-    for (int64_t w = o; w < stop; w++) {
+    for (int64_t w = w0; w < stop; w++) {
         while (w >= run_end) {
             i++;
             run_end = lit_off[i + 1];
-            from = i ? ev[i - 1].p + ev[i - 1].len : 0;
+            from = ev[i - 1].p + ev[i - 1].len;
         }
         s1[w] = buf[from++];
     }
 }
 
-extern "C" hipError_t mrz_launch_enc_size(hipStream_t stream, const mrz_event *ev, int64_t E, int64_t n, int cb,
-                                          int64_t *block_s0, int64_t *block_s1, mrz_enc_totals *totals) {
-    const int64_t nblocks = (E + 1 + MRZ_ENC_THREADS - 1) / MRZ_ENC_THREADS;
-    hipLaunchKernelGGL(mrz_enc_size_kernel, dim3((unsigned)nblocks), dim3(MRZ_ENC_THREADS), 0, stream, ev, E, n, cb,
-                       block_s0, block_s1);
+// one piece: E matches at ev[0..E), the first literal run from lit0, records from base0 / base1 of the two streams;
+// final_piece adds the trailing literal run up to n.  Leaves the piece's stream lengths in totals->s0_len / s1_len.
+extern "C" hipError_t mrz_launch_enc_size(hipStream_t stream, const mrz_event *ev, int64_t E, int final_piece,
+                                          int64_t lit0, int64_t n, int cb, int64_t *block_s0, int64_t *block_s1,
+                                          int64_t base0, int64_t base1, mrz_enc_totals *totals) {
+    const int64_t items = mrz_enc_items(E, final_piece);
+    const int64_t nblocks = (items + MRZ_ENC_THREADS - 1) / MRZ_ENC_THREADS;
+    if (nblocks > 0)
+        hipLaunchKernelGGL(mrz_enc_size_kernel, dim3((unsigned)nblocks), dim3(MRZ_ENC_THREADS), 0, stream, ev, E, items,
+                           lit0, n, cb, block_s0, block_s1);
     hipLaunchKernelGGL(mrz_enc_scan_kernel, dim3(1), dim3(MRZ_ENC_THREADS), 0, stream, block_s0, block_s1, nblocks,
-                       totals);
+                       base0, base1, totals);
     return hipGetLastError();
 }
 
+// s1_len: the piece's literal bytes (from mrz_launch_enc_size); they go to [base1, base1 + s1_len) of stream 1
 extern "C" hipError_t mrz_launch_enc_write(hipStream_t stream, const uint8_t *buf, const mrz_event *ev, int64_t E,
-                                           int64_t n, int cb, const int64_t *block_s0, const int64_t *block_s1,
-                                           uint8_t *s0, uint8_t *s1, int64_t s1_len, int64_t *lit_off,
-                                           mrz_enc_totals *totals, uint32_t crc) {
-    const int64_t nblocks = (E + 1 + MRZ_ENC_THREADS - 1) / MRZ_ENC_THREADS;
-    hipLaunchKernelGGL(mrz_enc_write_kernel, dim3((unsigned)nblocks), dim3(MRZ_ENC_THREADS), 0, stream, ev, E, n, cb,
-                       block_s0, block_s1, s0, lit_off, totals, crc);
+                                           int final_piece, int64_t lit0, int64_t n, int cb, const int64_t *block_s0,
+                                           const int64_t *block_s1, uint8_t *s0, uint8_t *s1, int64_t base1,
+                                           int64_t s1_len, int64_t *lit_off, mrz_enc_totals *totals, uint32_t crc) {
+    const int64_t items = mrz_enc_items(E, final_piece);
+    const int64_t nblocks = (items + MRZ_ENC_THREADS - 1) / MRZ_ENC_THREADS;
+    if (nblocks > 0)
+        hipLaunchKernelGGL(mrz_enc_write_kernel, dim3((unsigned)nblocks), dim3(MRZ_ENC_THREADS), 0, stream, ev, E, items,
+                           lit0, n, cb, block_s0, block_s1, s0, lit_off, totals, crc);
     if (s1_len > 0) {
-        const int64_t gblocks = (s1_len + MRZ_ENC_THREADS * 16 - 1) / (MRZ_ENC_THREADS * 16);
+        const int64_t span = base1 + s1_len - (base1 & ~(int64_t)15);
+        const int64_t gblocks = (span + MRZ_ENC_THREADS * 16 - 1) / (MRZ_ENC_THREADS * 16);
         hipLaunchKernelGGL(mrz_literal_gather_kernel, dim3((unsigned)gblocks), dim3(MRZ_ENC_THREADS), 0, stream, buf,
-                           ev, E, lit_off, s1_len, s1);
+                           ev, items, lit0, lit_off, base1, base1 + s1_len, s1);
     }
     return hipGetLastError();
 }

@@ -39,11 +39,14 @@ size_t mrz_seq_deep_shared_size(void);
 size_t mrz_sequencer_mailbox_size(void);
 size_t mrz_seq_narrow_mailbox_size(void);
 int mrz_sequencer_default_helpers(int device);
-hipError_t mrz_launch_enc_size(hipStream_t stream, const mrz_event *ev, int64_t E, int64_t n, int cb, int64_t *block_s0,
-                               int64_t *block_s1, mrz_enc_totals *totals);
-hipError_t mrz_launch_enc_write(hipStream_t stream, const uint8_t *buf, const mrz_event *ev, int64_t E, int64_t n,
-                                int cb, const int64_t *block_s0, const int64_t *block_s1, uint8_t *s0, uint8_t *s1,
-                                int64_t s1_len, int64_t *lit_off, mrz_enc_totals *totals, uint32_t crc);
+// the record encoder (mrz_encode.hip), one piece of a chunk's matches per call pair
+hipError_t mrz_launch_enc_size(hipStream_t stream, const mrz_event *ev, int64_t E, int final_piece, int64_t lit0,
+                               int64_t n, int cb, int64_t *block_s0, int64_t *block_s1, int64_t base0, int64_t base1,
+                               mrz_enc_totals *totals);
+hipError_t mrz_launch_enc_write(hipStream_t stream, const uint8_t *buf, const mrz_event *ev, int64_t E, int final_piece,
+                                int64_t lit0, int64_t n, int cb, const int64_t *block_s0, const int64_t *block_s1,
+                                uint8_t *s0, uint8_t *s1, int64_t base1, int64_t s1_len, int64_t *lit_off,
+                                mrz_enc_totals *totals, uint32_t crc);
 void mrz_crc_build_tables(mrz_crc_tables *tb);
 size_t mrz_crc_tables_size(void);
 int64_t mrz_crc32_parts_needed(int64_t n);

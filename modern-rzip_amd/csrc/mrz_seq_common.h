@@ -655,6 +655,7 @@ struct mrz_cfg {
     mrz_event *events;
     mrz_seq_state *st;
     int64_t end, limit, max_chain, slot_mask, nslots, event_cap;
+    int64_t ev_base;           // absolute index of events[0] (the host encodes the list in pieces: mrz_capi.hip)
     mrz_gmailbox *gmb;
     unsigned long long *gseq;  // leader's copy of the global round counter
     int *gnw;                  // helper tickets the leader has seen so far
@@ -675,7 +676,7 @@ __device__ __forceinline__ bool mrz_select_emit(const mrz_cfg &C, mrz_lead &L, i
         L.cur_ofs = m_off;
     }
     if ((L.cur_len >= MRZ_GREAT_MATCH || L.p >= L.cur_p + MRZ_MIN_MATCH) && L.cur_len >= MRZ_MIN_MATCH) {
-        if (L.n_events >= C.event_cap) {  // cannot happen: matches are >= 31 bytes and disjoint
+        if (L.n_events - C.ev_base >= C.event_cap) {  // cannot happen: the host drains the list before it can fill
             if (lane == 0) C.st->error = 1;
             return false;
         }
@@ -684,7 +685,7 @@ __device__ __forceinline__ bool mrz_select_emit(const mrz_cfg &C, mrz_lead &L, i
             ev.p = L.cur_p;
             ev.ofs = L.cur_ofs;
             ev.len = L.cur_len;
-            C.events[L.n_events] = ev;
+            C.events[L.n_events - C.ev_base] = ev;
         }
         L.n_events++;
         L.last_len = L.cur_len;

@@ -2018,7 +2018,7 @@ __device__ static void mrz_wide_commit(const mrz_cfg &C, mrz_lead &L, mrz_wide_l
         if (emission) {
             ST_ADD(MRZ_ST_EMITS, 1);
             const int64_t q_e = L.p;
-            if (L.n_events >= C.event_cap) {  // cannot happen: matches are >= 31 bytes and disjoint
+            if (L.n_events - C.ev_base >= C.event_cap) {  // cannot happen: the host drains the list before it can fill
                 if (lane == 0) C.st->error = 1;
                 ret->ok = false;
                 break;
@@ -2028,7 +2028,7 @@ __device__ static void mrz_wide_commit(const mrz_cfg &C, mrz_lead &L, mrz_wide_l
                 ev.p = L.cur_p;
                 ev.ofs = L.cur_ofs;
                 ev.len = L.cur_len;
-                C.events[L.n_events] = ev;
+                C.events[L.n_events - C.ev_base] = ev;
             }
             L.n_events++;
             L.last_len = L.cur_len;

@@ -156,6 +156,7 @@ __global__ __launch_bounds__(MRZ_SEQ_THREADS) void mrz_sequencer_kernel(mrz_seq_
     C.slot_mask = st->slot_mask;
     C.nslots = st->slot_mask + 1;
     C.event_cap = st->event_cap;
+    C.ev_base = st->ev_base;
     C.gmb = (mrz_gmailbox *)a.gmailbox;
     unsigned long long gseq = 0;
     C.gseq = &gseq;
