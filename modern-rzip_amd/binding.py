@@ -163,6 +163,11 @@ def load_library(path=None):
                                                ctypes.POINTER(i64), ctypes.POINTER(Stats), ctypes.c_char_p]
         lib.mrz_free.argtypes = [vp]
         lib.mrz_free.restype = None
+    if hasattr(lib, "mrz_synth_tar"):  # include/mrzgpu_synth.h
+        u64 = ctypes.c_uint64
+        lib.mrz_synth_noise.argtypes = [vp, vp, i64, i64, u64]
+        lib.mrz_synth_text.argtypes = [vp, vp, i64, u64, u64]
+        lib.mrz_synth_tar.argtypes = [vp, vp, i64, i64, vp, i64, u64]
     if path is None:
         _lib = lib
     return lib
@@ -397,6 +402,35 @@ class RzipContext:
         out = ctypes.c_uint32()
         _check(self.lib, self.lib.mrz_crc32(self.ctx, ptr, n, where, ctypes.byref(out)), self.ctx)
         return out.value
+
+    # ---- reproducible workload streams (include/mrzgpu_synth.h) ----
+    def _synth_out(self, out, nbytes):
+        if not hasattr(self.lib, "mrz_synth_tar"):
+            raise MrzError("this libmrzgpu has no mrz_synth_* (include/mrzgpu_synth.h): rebuild it")
+        ptr, n, where, keep = _as_ptr(out)
+        if n < nbytes:
+            raise MrzError("synth: the output buffer is smaller than the range asked for")
+        return ptr
+
+    def synth_noise(self, out, nbytes, seed, start=0):
+        """Fills `out` (a tensor or (pointer, nbytes) in the ctx's memory space: device memory on the GPU) with bytes
+        [start, start + nbytes) of noise(seed)."""
+        _check(self.lib, self.lib.mrz_synth_noise(self.ctx, self._synth_out(out, nbytes), start, nbytes, seed), self.ctx)
+
+    def synth_text(self, out, nbytes, seed, vocab_seed):
+        """Fills `out` with the first nbytes of text(seed, vocab_seed)."""
+        _check(self.lib, self.lib.mrz_synth_text(self.ctx, self._synth_out(out, nbytes), nbytes, seed, vocab_seed),
+               self.ctx)
+
+    def synth_tar(self, out, nbytes, plan, vocab_seed, start=0):
+        """Fills `out` with bytes [start, start + nbytes) of the tar stream whose members `plan` lists (a numpy array of
+        workloads.SYNTH_MEMBER, as workloads.synth_tar_plan returns it)."""
+        import numpy as np
+        plan = np.ascontiguousarray(plan)
+        if plan.dtype.itemsize != 32:
+            raise MrzError("synth_tar: plan must be an array of workloads.SYNTH_MEMBER")
+        _check(self.lib, self.lib.mrz_synth_tar(self.ctx, self._synth_out(out, nbytes), start, nbytes,
+                                                ctypes.c_void_p(plan.ctypes.data), len(plan), vocab_seed), self.ctx)
 
     # ---- LZ4 gate (src/stream.c:1685-1733) ----
     def lz4_compresses(self, blocks, threshold=100):
