@@ -76,7 +76,8 @@ typedef struct {
 typedef struct {
     float tagscan_ms;   /* sum over segments */
     float sequencer_ms; /* sum over segments */
-    float encode_ms;
+    float encode_ms;    /* the stream encoder of the last chunk; after mrz_rs_encode its kernel, after mrz_rs_decode /
+                         * mrz_rs_decode_ex the two decode kernels together (syndromes + repair) */
     float crc_ms;
     float total_ms;     /* first launch -> last kernel done */
     int32_t n_segments; /* sequencer launches (segments an emitted match has covered are not launched) */
@@ -302,6 +303,26 @@ typedef struct {
 } mrz_rs_report;
 int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out_host, int64_t out_cap, int64_t *out_len,
                   mrz_rs_report *rep);
+
+/* The same decode with the output where the caller wants it and one status per codeword.
+ *   out / out_where   host or device memory, as in mrz_rs_encode; out_cap at least (n / 2084880) * 1823248 bytes, else
+ *                     MRZ_E_ARG.  *out_len: what `rs-mrzip -d` would write (padding stripped by {k_i, k_j}; nothing
+ *                     stripped when the trailer is missing).
+ *   row_status        NULL, or mrz_rs_codewords(n) entries in host or device memory (status_where).  Entry
+ *                     b * 8176 + r is what rsd32 returns for row r of burst b: 0 = clean, > 0 = that many bytes
+ *                     corrected (parity bytes included), -1 = uncorrectable, the row is left as it came.  Row i
+ *                     covers output bytes [223 i, 223 i + 223).
+ *   flags             MRZ_RS_SKIP_CHECKSUM: the BLAKE2b comparison is not made and rep->checksum_ok = -1; with device
+ *                     output nothing but the 68-byte trailer and the 24 bytes of totals come to the host.  Without
+ *                     the flag the check is made as in mrz_rs_decode; for device output the rows are copied out to
+ *                     be hashed.  The hash stays on a host thread: it is one serial BLAKE2b chain, which the device
+ *                     runs at 24 MB/s, far below what a host core does.
+ * Damaged codewords are repaired on the device, one wave per codeword; the call waits for the
+ * stream once.  mrz_rs_decode is this call with host output, no status and flags 0. */
+#define MRZ_RS_SKIP_CHECKSUM 1
+int64_t mrz_rs_codewords(int64_t n); /* (n / 2084880) * 8176; 0 when n holds no whole burst */
+int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where, int64_t out_cap,
+                     int64_t *out_len, int32_t *row_status, int status_where, int flags, mrz_rs_report *rep);
 
 /* ---- runzip: decoder of the two rzip streams of a chunk ---------- */
 

@@ -98,6 +98,11 @@ def load_library(path=None):
     lib.mrz_last_hip_error.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p)]
     if hasattr(lib, "mrz_rs_decode"):
         lib.mrz_rs_decode.argtypes = [vp, vp, i64, ci, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(RsReport)]
+    if hasattr(lib, "mrz_rs_decode_ex"):
+        lib.mrz_rs_codewords.argtypes = [i64]
+        lib.mrz_rs_codewords.restype = i64
+        lib.mrz_rs_decode_ex.argtypes = [vp, vp, i64, ci, vp, ci, i64, ctypes.POINTER(i64), vp, ci, ci,
+                                         ctypes.POINTER(RsReport)]
     if hasattr(lib, "mrz_window_scan"):
         i64p = ctypes.POINTER(i64)
         lib.mrz_window_scan.argtypes = [vp, vp, i64, ci, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, ci, i64p, i64p]
@@ -476,6 +481,46 @@ class RzipContext:
                self.ctx)
         return out.raw[:out_len.value], dict(corrected=rep.corrected, uncorrectable=rep.uncorrectable,
                                              checksum_ok=bool(rep.checksum_ok), truncated=bool(rep.truncated))
+
+    def rs_decode_ex(self, data, out=None, status=True, skip_checksum=False):
+        """mrz_rs_decode_ex -> (bytes or None, report, int32 numpy array or None).  report: corrected, uncorrectable,
+        checksum_ok (-1: not checked), truncated.  status: True = one entry per codeword (0 clean, > 0 bytes corrected,
+        -1 uncorrectable) as a numpy array; a cuda int32 tensor or a (device pointer, nbytes) pair = filled on the
+        device and returned as it is; False/None = not asked for.  With `out` = a cuda tensor or a (device pointer,
+        nbytes) pair the bytes stay on the device and the report gains out_len."""
+        import numpy as np
+        if not hasattr(self.lib, "mrz_rs_decode_ex"):
+            raise MrzError("this libmrzgpu has no mrz_rs_decode_ex: rebuild it")
+        ptr, n, where, keep = _as_ptr(data)
+        cap = (n // 2084880) * 1823248
+        rows = self.lib.mrz_rs_codewords(n)
+        st_arr, st_ptr, st_where, st_keep = None, None, MEM_HOST, None
+        if status is True:
+            st_arr = np.empty(rows, dtype=np.int32)
+            st_ptr = ctypes.c_void_p(st_arr.ctypes.data)
+        elif status is not None and status is not False:
+            st_ptr, st_n, st_where, st_keep = _as_ptr(status)
+            if st_where != MEM_DEVICE or st_n < rows * 4:
+                raise MrzError("rs_decode_ex: status must be device memory of 4 bytes per codeword")
+            st_arr = status
+        out_len = ctypes.c_int64()
+        rep = RsReport()
+        flags = 1 if skip_checksum else 0  # MRZ_RS_SKIP_CHECKSUM
+        if out is None:
+            buf = ctypes.create_string_buffer(max(cap, 1))
+            po, no, wo = ctypes.cast(buf, ctypes.c_void_p), cap, MEM_HOST
+        else:
+            po, no, wo, ko = _as_ptr(out)
+            if wo != MEM_DEVICE:
+                raise MrzError("rs_decode_ex: out must be device memory (leave it out for bytes)")
+        _check(self.lib, self.lib.mrz_rs_decode_ex(self.ctx, ptr, n, where, po, wo, no, ctypes.byref(out_len), st_ptr,
+                                                   st_where, flags, ctypes.byref(rep)), self.ctx)
+        report = dict(corrected=rep.corrected, uncorrectable=rep.uncorrectable,
+                      checksum_ok=-1 if rep.checksum_ok < 0 else bool(rep.checksum_ok), truncated=bool(rep.truncated))
+        if out is None:
+            return buf.raw[:out_len.value], report, st_arr
+        report["out_len"] = out_len.value
+        return None, report, st_arr
 
     # ---- runzip (src/runzip.c:120-207,277-308) ----
     def runzip_chunk(self, s0, s1, chunk_bytes_, out_cap, out=None):

@@ -72,6 +72,8 @@ struct mrz_ctx {
     void *d_rs_tables;  // Reed-Solomon tables (mrz_rs.hip)
     uint8_t *d_rs_out;
     int64_t rs_out_cap;
+    uint8_t *d_rs_dec;  // decoder scratch: totals, row statuses, the list of damaged rows
+    int64_t rs_dec_cap;
     void *rz_scratch;  // runzip: parse tables, records, staged streams (mrz_runzip.hip)
     int64_t rz_scratch_cap;
     uint8_t *d_rz_out;

@@ -80,6 +80,26 @@ static void mrz_rs_build_tables(mrz_rs_tables *T) {
     T->lg[0] = 255;
 }
 
+// the tables, built and uploaded on a ctx's first Reed-Solomon call
+static int mrz_rs_need_tables(mrz_ctx *ctx) {
+    if (ctx->d_rs_tables) return MRZ_OK;
+    mrz_rs_tables *T = (mrz_rs_tables *)malloc(sizeof(mrz_rs_tables));
+    void *p = nullptr;
+    hipError_t e = T ? hipMalloc(&p, sizeof(mrz_rs_tables)) : hipErrorOutOfMemory;
+    if (e == hipSuccess) {
+        mrz_rs_build_tables(T);
+        e = hipMemcpy(p, T, sizeof(mrz_rs_tables), hipMemcpyHostToDevice);
+    }
+    free(T);
+    if (e != hipSuccess) {
+        if (p) hipFree(p);
+        ctx->last_err = e;
+        return MRZ_E_NOMEM;
+    }
+    ctx->d_rs_tables = p;
+    return MRZ_OK;
+}
+
 // grid.x = bursts * 73; each workgroup: 112 rows of one burst
 __global__ __launch_bounds__(MRZ_RS_THREADS) void mrz_rs_encode_kernel(const uint8_t *__restrict__ in, int64_t n,
                                                                        const mrz_rs_tables *__restrict__ T,
@@ -319,21 +339,10 @@ extern "C" int mrz_rs_encode(mrz_ctx *ctx, const void *in, int64_t n, int where,
         b.final(digest);
     });
 
-    if (!ctx->d_rs_tables) {
-        mrz_rs_tables *T = (mrz_rs_tables *)malloc(sizeof(mrz_rs_tables));
-        void *p = nullptr;
-        hipError_t e = T ? hipMalloc(&p, sizeof(mrz_rs_tables)) : hipErrorOutOfMemory;
-        if (e == hipSuccess) {
-            mrz_rs_build_tables(T);
-            e = hipMemcpy(p, T, sizeof(mrz_rs_tables), hipMemcpyHostToDevice);
-        }
-        free(T);
-        if (e != hipSuccess) {
-            hasher.join();
-            ctx->last_err = e;
-            return MRZ_E_NOMEM;
-        }
-        ctx->d_rs_tables = p;
+    rc = mrz_rs_need_tables(ctx);
+    if (rc) {
+        hasher.join();
+        return rc;
     }
     uint8_t *d_out = (uint8_t *)out;
     if (out_where == MRZ_MEM_HOST) {
@@ -387,98 +396,60 @@ extern "C" int mrz_rs_encode(mrz_ctx *ctx, const void *in, int64_t n, int where,
 
 
 // ---- rs-mrzip decoder (rs-mrzip/rs-mrzip.c:37-117 decode(), reed-solomon.c:143-309 rsd32, :323-333 gather) ------
-// One lane per codeword: the 8176 rows of a burst are independent.  A workgroup takes 128 rows: the interleaved
-// input is read column by column (byte c of row r at c * 8176 + r: coalesced across the lanes), converted to the
-// conventional basis (tal1tab) into an LDS image, and the 32 syndromes are accumulated on the way.  Rows whose
-// syndromes vanish -- all of them on undamaged input -- are done; the others run Berlekamp-Massey, the Chien search
-// and Forney's formula exactly as rsd32 does (same field, same roots alpha^(11 (112 + i)), same order of operations,
-// so that miscorrections and "uncorrectable" verdicts agree too), each lane on its own row.  The image goes back
-// through taltab and out as 223 data bytes per row, row-major.
+// Two kernels on one stream, no host read-back between them.
+//
+// mrz_rs_decode_kernel, one lane per codeword: the 8176 rows of a burst are independent.  A workgroup takes 128 rows:
+// the interleaved input is read column by column (byte c of row r at c * 8176 + r: coalesced across the lanes), kept
+// in an LDS image, and the 32 syndromes s[i] = row(alpha^(11 (111 + i))) of its dual->conventional image are
+// accumulated on the way.  The 223 data bytes of every row go out as they came, row-major (taltab o tal1tab =
+// identity).  Rows whose syndromes vanish -- all of them on undamaged input -- get status 0 and are done; every other
+// row is appended to a device list as {row, 32 syndromes in index form}: one agent-scope atomic per wave reserves the
+// slots of all its damaged rows.
+//
+// mrz_rs_repair_kernel, one WAVE per codeword: a fixed grid whose waves stride over that list.  Repair needs the
+// syndromes only.  The error locator, its roots and the error values are those of rsd32 -- same field, same syndromes,
+// Berlekamp-Massey over 32 steps without erasures, Chien points i = 1..255 with location 139 i mod 255, Forney with
+// alpha^(111 i) -- so corrected bytes, counts and "uncorrectable" verdicts (miscorrections included) agree with it;
+// the work is laid across the lanes instead of arrays:
+//   * lane i (0..32) holds lambda_i and b_i; the discrepancy of step r is the XOR of the terms lambda_i s[r-i], which
+//     the lanes put side by side in LDS and every lane folds for itself; the shift of b goes the same way;
+//   * the 255 Chien points are 4 passes of 64, one point per lane and pass, evaluated together (lambda_j is
+//     one broadcast read per j); ballots count the roots.  The sum over the odd j is kept apart: the derivative
+//     rsd32 divides by, sum_{j odd} lambda_j x^(j-1), is that sum times x^-1;
+//   * lane i (0..31) forms omega_i = sum_j s[i+1-j] lambda_j, and every lane evaluates omega at its four points the
+//     same way; the lanes whose point is a root then hold numerator and denominator of their error value.
+// The value e of column loc is XORed into the output where kernel 1 left the row: taltab is GF(2)-linear (built by
+// XOR of basis images), so tal[a ^ e] = tal[a] ^ tal[e] and the conventional-basis row image is not needed.  Columns
+// 223..254 are parity: counted, not part of the output.  A locator with deg distinct roots is separable, so its
+// derivative cannot vanish at one of them (rsd32's `den == 0` exit is dead code once the root count matches); a guard
+// reports -1 all the same.  Roots are distinct columns, so the order they are applied in does not matter.
 #define MRZ_RSD_ROWS 128
 #define MRZ_RSD_STRIDE 260  // bytes per LDS row (65 words: lanes of a wave hit different banks)
+#define MRZ_RSR_THREADS 256  // repair kernel: 4 waves per workgroup
+#define MRZ_RSR_WGS_PER_CU 8
 
-__device__ static int mrz_rsd_slow(uint8_t *data, const int *s_in, const uint8_t *ex, const uint8_t *lg) {
-    // s_in[1..32]: syndromes in index form (255 = zero).  no_eras = 0 (rs-mrzip never passes erasures).
-    int lambda[33], b[33], t[33], omega[33], reg[33], root[32], loc[32], s[33];
-    for (int i = 1; i <= 32; i++) s[i] = s_in[i];
-    for (int i = 0; i < 33; i++) lambda[i] = 0;
-    lambda[0] = 1;
-    for (int i = 0; i < 33; i++) b[i] = lg[lambda[i]];
-    int r = 0, el = 0;
-    while (++r <= 32) {  // Berlekamp-Massey, :203-232
-        int discr = 0;
-        for (int i = 0; i < r; i++)
-            if (lambda[i] != 0 && s[r - i] != 255) discr ^= ex[(lg[lambda[i]] + s[r - i]) % 255];
-        discr = lg[discr];
-        if (discr == 255) {
-            for (int i = 32; i > 0; i--) b[i] = b[i - 1];
-            b[0] = 255;
-        } else {
-            t[0] = lambda[0];
-            for (int i = 0; i < 32; i++) t[i + 1] = b[i] != 255 ? (lambda[i + 1] ^ ex[(discr + b[i]) % 255]) : lambda[i + 1];
-            if (2 * el <= r - 1) {
-                el = r - el;
-                for (int i = 0; i <= 32; i++) b[i] = lambda[i] == 0 ? 255 : (lg[lambda[i]] - discr + 255) % 255;
-            } else {
-                for (int i = 32; i > 0; i--) b[i] = b[i - 1];
-                b[0] = 255;
-            }
-            for (int i = 0; i < 33; i++) lambda[i] = t[i];
-        }
-    }
-    int deg_lambda = 0;
-    for (int i = 0; i < 33; i++) {
-        lambda[i] = lg[lambda[i]];
-        if (lambda[i] != 255) deg_lambda = i;
-    }
-    for (int i = 1; i <= 32; i++) reg[i] = lambda[i];
-    int count = 0;
-    for (int i = 1, k = 139; i <= 255; i++, k = (k + 139) % 255) {  // Chien search, :244-258
-        int q = 1;
-        for (int j = deg_lambda; j > 0; j--)
-            if (reg[j] != 255) {
-                reg[j] = (reg[j] + j) % 255;
-                q ^= ex[reg[j]];
-            }
-        if (q != 0) continue;
-        root[count] = i;
-        loc[count] = k;
-        if (++count == deg_lambda) break;
-    }
-    if (deg_lambda != count) return -1;  // uncorrectable, :259-264
-    int deg_omega = 0;
-    for (int i = 0; i < 32; i++) {  // omega(x) = s(x) lambda(x) mod x^32, :267-276
-        int tmp = 0;
-        for (int j = deg_lambda < i ? deg_lambda : i; j >= 0; j--)
-            if (s[i + 1 - j] != 255 && lambda[j] != 255) tmp ^= ex[(s[i + 1 - j] + lambda[j]) % 255];
-        if (tmp != 0) deg_omega = i;
-        omega[i] = lg[tmp];
-    }
-    omega[32] = 255;
-    for (int j = count - 1; j >= 0; j--) {  // Forney, :280-301
-        int num1 = 0;
-        for (int i = deg_omega; i >= 0; i--)
-            if (omega[i] != 255) num1 ^= ex[(omega[i] + i * root[j]) % 255];
-        const int num2 = ex[(root[j] * 111) % 255];
-        int den = 0;
-        for (int i = (deg_lambda < 31 ? deg_lambda : 31) & ~1; i >= 0; i -= 2)
-            if (lambda[i + 1] != 255) den ^= ex[(lambda[i + 1] + i * root[j]) % 255];
-        if (den == 0) return -1;  // (what has been applied so far stays applied, as in the reference)
-        if (num1 != 0) data[loc[j]] ^= ex[(lg[num1] + lg[num2] + 255 - lg[den]) % 255];
-    }
-    return count;
-}
+struct mrz_rsd_entry {
+    int row;        // global codeword index: burst * 8176 + row of the burst
+    uint32_t s[8];  // s[1..32] in index form (255 = zero), s[i] in byte i - 1
+};
+struct mrz_rsd_head {
+    unsigned long long corrected;      // sum of the positive statuses
+    unsigned long long uncorrectable;  // number of -1 statuses
+    unsigned n_listed;                 // entries of the list
+    unsigned pad;
+};
 
-__global__ __launch_bounds__(MRZ_RSD_ROWS) void mrz_rs_decode_kernel(const uint8_t *__restrict__ in, int64_t nbursts,
+__global__ __launch_bounds__(MRZ_RSD_ROWS) void mrz_rs_decode_kernel(const uint8_t *__restrict__ in,
                                                                      const mrz_rs_tables *__restrict__ T,
-                                                                     uint8_t *__restrict__ out, int *__restrict__ counts) {
-    __shared__ uint8_t s_ex[256], s_lg[256], s_tal[256], s_tal1[256];
+                                                                     uint8_t *__restrict__ out, int *__restrict__ counts,
+                                                                     mrz_rsd_head *__restrict__ head,
+                                                                     mrz_rsd_entry *__restrict__ list) {
+    __shared__ uint8_t s_ex[256], s_lg[256], s_tal1[256];
     __shared__ __attribute__((aligned(4))) uint8_t s_img[MRZ_RSD_ROWS * MRZ_RSD_STRIDE];
     const int tid = threadIdx.x;
     for (int i = tid; i < 256; i += MRZ_RSD_ROWS) {
         s_ex[i] = T->ex[i];
         s_lg[i] = T->lg[i];
-        s_tal[i] = T->tal[i];
         s_tal1[i] = T->tal1[i];
     }
     __syncthreads();
@@ -488,7 +459,8 @@ __global__ __launch_bounds__(MRZ_RSD_ROWS) void mrz_rs_decode_kernel(const uint8
     const int nrows = MRZ_RS_ROWS - row0 < MRZ_RSD_ROWS ? MRZ_RS_ROWS - row0 : MRZ_RSD_ROWS;
     const uint8_t *src = in + burst * (int64_t)MRZ_RS_N * MRZ_RS_ROWS + row0;
     uint8_t *row = &s_img[tid * MRZ_RSD_STRIDE];
-    int count = 0;
+    int syn_error = 0;
+    uint32_t sw[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };  // the syndromes in index form, four to a dword
     if (tid < nrows) {
         // gather + dual -> conventional + syndromes: s[i] = sum_j data[j] alpha^((111 + i) 11 j), :156-166
         int s[33], pw[33];
@@ -498,8 +470,9 @@ __global__ __launch_bounds__(MRZ_RSD_ROWS) void mrz_rs_decode_kernel(const uint8
             pw[i] = 0;
         }
         for (int c = 0; c < MRZ_RS_N; c++) {
-            const int d = s_tal1[src[(int64_t)c * MRZ_RS_ROWS + tid]];
-            row[c] = (uint8_t)d;
+            const uint8_t raw = src[(int64_t)c * MRZ_RS_ROWS + tid];
+            row[c] = raw;
+            const int d = s_tal1[raw];
             if (d != 0) {
                 const int lgd = s_lg[d];
 #pragma unroll
@@ -515,28 +488,218 @@ __global__ __launch_bounds__(MRZ_RSD_ROWS) void mrz_rs_decode_kernel(const uint8
                 pw[i] = e >= 255 ? e - 255 : e;
             }
         }
-        int syn_error = 0;
 #pragma unroll
         for (int i = 1; i <= 32; i++) {
             syn_error |= s[i];
-            s[i] = s_lg[s[i]];
+            sw[(i - 1) >> 2] |= (uint32_t)s_lg[s[i]] << (8 * ((i - 1) & 3));
         }
-        if (syn_error) count = mrz_rsd_slow(row, s, s_ex, s_lg);
-        counts[burst * MRZ_RS_ROWS + row0 + tid] = count;
+        if (!syn_error) counts[burst * MRZ_RS_ROWS + row0 + tid] = 0;
+    }
+    // damaged rows go to the list: the wave's first damaged lane reserves the slots of all of them
+    const unsigned long long damaged = __ballot(syn_error != 0);
+    if (damaged) {
+        const int lane = tid & 63;
+        const int leader = __ffsll((long long)damaged) - 1;
+        int base = 0;
+        if (lane == leader)
+            base = (int)__hip_atomic_fetch_add(&head->n_listed, (unsigned)__popcll(damaged), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+        base = __shfl(base, leader);
+        if (syn_error) {
+            mrz_rsd_entry *e = &list[base + __popcll(damaged & ((1ull << lane) - 1))];
+            e->row = (int)(burst * MRZ_RS_ROWS + row0 + tid);
+#pragma unroll
+            for (int k = 0; k < 8; k++) e->s[k] = sw[k];
+        }
     }
     __syncthreads();
-    // the data bytes of the rows, back in the dual basis (taltab, :305), row-major
+    // the data bytes of the rows, row-major
     uint8_t *dst = out + (burst * MRZ_RS_ROWS + row0) * (int64_t)MRZ_RS_K;
     for (int idx = tid; idx < nrows * MRZ_RS_K; idx += MRZ_RSD_ROWS) {
         const int r = idx / MRZ_RS_K, c = idx % MRZ_RS_K;
-        dst[idx] = s_tal[s_img[r * MRZ_RSD_STRIDE + c]];
+        dst[idx] = s_img[r * MRZ_RSD_STRIDE + c];
     }
-    (void)nbursts;
 }
 
-extern "C" int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out_host, int64_t out_cap,
-                             int64_t *out_len, mrz_rs_report *rep) {
-    if (!ctx || !in || !out_host || !out_len || n < 0) return MRZ_E_ARG;
+// grid: any; the waves stride over the list.  The lanes of a wave hand values to each other through a piece of LDS
+// that belongs to the wave: a wave's LDS operations execute in program order, so what every lane stored before a
+// ballot is there for all of them after it (the accesses are volatile: the compiler keeps their order too).  The
+// ballot itself is the point where the lanes meet when the wave is emulated by fibers, which is also why a value that
+// is rewritten every Berlekamp-Massey step has two slots, used in turn.  All 64 lanes run every ballot: the loop
+// bounds and branches around them are wave-uniform.
+struct mrz_rsr_wave {
+    uint8_t syn[64];      // [i] = s[i], index form, for i = 1..32; 255 elsewhere
+    uint8_t term[2][32];  // the terms lambda_i s[r-i] of a step's discrepancy
+    uint8_t b[2][40];     // [i + 1] = b_i of a step; [0] = 255, what is shifted in
+    uint8_t lam[36];      // lambda in index form
+    uint8_t om[32];       // omega in index form
+};
+
+__global__ __launch_bounds__(MRZ_RSR_THREADS) void mrz_rs_repair_kernel(const mrz_rs_tables *__restrict__ T,
+                                                                        const mrz_rsd_entry *__restrict__ list,
+                                                                        mrz_rsd_head *__restrict__ head,
+                                                                        uint8_t *__restrict__ out, int *__restrict__ counts) {
+    __shared__ uint8_t s_ex[512];  // alpha^i for i = 0..509: the sum of two index forms needs no reduction mod 255
+    __shared__ uint8_t s_lg[256], s_tal[256];
+    __shared__ __attribute__((aligned(16))) mrz_rsr_wave s_wave[MRZ_RSR_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int i = tid; i < 512; i += MRZ_RSR_THREADS) s_ex[i] = i < 510 ? T->ex[i < 255 ? i : i - 255] : (uint8_t)0;
+    for (int i = tid; i < 256; i += MRZ_RSR_THREADS) {
+        s_lg[i] = T->lg[i];
+        s_tal[i] = T->tal[i];
+    }
+    volatile mrz_rsr_wave *W = &s_wave[tid / 64];
+    if (lane < 2) W->b[lane][0] = 255;
+    __syncthreads();
+    const unsigned n_listed = head->n_listed;  // complete: the kernel that wrote it ran before this one
+    const unsigned n_waves = gridDim.x * (MRZ_RSR_THREADS / 64);
+    unsigned long long corrected = 0, lost = 0;  // of this wave's codewords (wave-uniform)
+    // the four Chien points of this lane, i = lane + 1 + 64 p, and i mod 255 (point 256 does not exist)
+    int pt[4], step[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        pt[p] = lane + 1 + 64 * p;
+        step[p] = pt[p] >= 255 ? pt[p] - 255 : pt[p];
+    }
+    for (unsigned k = blockIdx.x * (MRZ_RSR_THREADS / 64) + tid / 64; k < n_listed; k += n_waves) {
+        const mrz_rsd_entry *ent = &list[k];
+        const int row = ent->row;
+        W->syn[lane] = lane >= 1 && lane <= 32 ? reinterpret_cast<const uint8_t *>(ent->s)[lane - 1] : (uint8_t)255;
+
+        // Berlekamp-Massey: lambda in polynomial form, b in index form, coefficient i on lane i (0..32)
+        int lam = lane == 0 ? 1 : 0, b = lane == 0 ? 0 : 255, el = 0;
+        (void)__ballot(1);  // syn is there
+#pragma unroll 1
+        for (int r = 1; r <= 32; r++) {
+            const int slot = r & 1;
+            if (lane < 32) {
+                int t = 0;
+                if (lane < r && lam != 0) {
+                    const int sv = W->syn[r - lane];
+                    if (sv != 255) t = s_ex[s_lg[lam] + sv];
+                }
+                W->term[slot][lane] = (uint8_t)t;
+            }
+            if (lane <= 32) W->b[slot][lane + 1] = (uint8_t)b;
+            (void)__ballot(1);
+            const volatile uint32_t *tw = reinterpret_cast<const volatile uint32_t *>(&W->term[slot][0]);
+            uint32_t x = tw[0] ^ tw[1] ^ tw[2] ^ tw[3] ^ tw[4] ^ tw[5] ^ tw[6] ^ tw[7];
+            x ^= x >> 16;
+            x ^= x >> 8;
+            const int d = s_lg[x & 0xff];                    // the discrepancy, index form
+            const int bdown = lane <= 32 ? (int)W->b[slot][lane] : 255;  // b of the coefficient below
+            if (d == 255) {
+                b = bdown;
+            } else {
+                const int t = bdown != 255 ? lam ^ (int)s_ex[d + bdown] : lam;
+                if (2 * el <= r - 1) {
+                    el = r - el;
+                    const int q = (int)s_lg[lam] - d + 255;
+                    b = lam == 0 ? 255 : (q >= 255 ? q - 255 : q);
+                } else
+                    b = bdown;
+                lam = t;
+            }
+        }
+        const int lidx = s_lg[lam];  // index form; lanes above 32 hold zero
+        if (lane <= 32) W->lam[lane] = (uint8_t)lidx;
+        unsigned long long nz = __ballot(lidx != 255);  // bit 0 is set: lambda_0 = 1
+        nz |= nz >> 1;
+        nz |= nz >> 2;
+        nz |= nz >> 4;
+        nz |= nz >> 8;
+        nz |= nz >> 16;
+        nz |= nz >> 32;
+        const int deg = __popcll(nz) - 1;
+
+        // Chien search: lambda(alpha^i) at the four points of the lane; the terms of odd j also on their own
+        int ev[4] = { 1, 1, 1, 1 }, odd[4] = { 0, 0, 0, 0 }, e[4] = { 0, 0, 0, 0 };
+#pragma unroll 1
+        for (int j = 1; j <= deg; j++) {
+            const int lj = W->lam[j];
+#pragma unroll
+            for (int p = 0; p < 4; p++) {  // i j mod 255
+                const int x = e[p] + step[p];
+                e[p] = x >= 255 ? x - 255 : x;
+            }
+            if (lj != 255) {
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    const int v = s_ex[lj + e[p]];
+                    ev[p] ^= v;
+                    if (j & 1) odd[p] ^= v;
+                }
+            }
+        }
+        int nroots = 0, no_den = 0;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int is_root = pt[p] <= 255 && ev[p] == 0;
+            nroots += __popcll(__ballot(is_root));
+            no_den |= is_root && odd[p] == 0;
+        }
+        int status = deg;
+        if (nroots != deg || __ballot(no_den)) {
+            status = -1;  // uncorrectable: the row stays as it came
+        } else {
+            // omega(x) = s(x) lambda(x) mod x^32, coefficient i on lane i, index form
+            if (lane < 32) {
+                int om = 0;
+                const int top = deg < lane ? deg : lane;
+#pragma unroll 1
+                for (int j = 0; j <= top; j++) {
+                    const int lj = W->lam[j], sv = W->syn[lane + 1 - j];
+                    if (lj != 255 && sv != 255) om ^= s_ex[lj + sv];
+                }
+                W->om[lane] = s_lg[om];
+            }
+            (void)__ballot(1);
+            int num[4] = { 0, 0, 0, 0 };
+#pragma unroll
+            for (int p = 0; p < 4; p++) e[p] = 0;
+#pragma unroll 1
+            for (int c = 0; c < 32; c++) {  // omega(alpha^i)
+                const int oc = W->om[c];
+                if (oc != 255) {
+#pragma unroll
+                    for (int p = 0; p < 4; p++) num[p] ^= s_ex[oc + e[p]];
+                }
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    const int x = e[p] + step[p];
+                    e[p] = x >= 255 ? x - 255 : x;
+                }
+            }
+            // Forney: value = omega(x) x^111 / lambda'(x) at x = alpha^i, and lambda'(x) = x^-1 * (odd terms)
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                if (pt[p] <= 255 && ev[p] == 0 && num[p] != 0) {
+                    const int loc = (139 * pt[p]) % 255;
+                    const int x = ((int)s_lg[num[p]] + (112 * step[p]) % 255 + 255 - (int)s_lg[odd[p]]) % 255;
+                    if (loc < MRZ_RS_K) out[(int64_t)row * MRZ_RS_K + loc] ^= s_tal[s_ex[x]];
+                }
+            }
+        }
+        if (lane == 0) counts[row] = status;
+        if (status > 0) corrected += (unsigned long long)status;
+        if (status < 0) lost++;
+    }
+    if (lane == 0) {
+        if (corrected) atomicAdd(&head->corrected, corrected);
+        if (lost) atomicAdd(&head->uncorrectable, lost);
+    }
+}
+
+extern "C" int64_t mrz_rs_codewords(int64_t n) {
+    return n < 0 ? 0 : n / ((int64_t)MRZ_RS_N * MRZ_RS_ROWS) * MRZ_RS_ROWS;
+}
+
+extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where,
+                                int64_t out_cap, int64_t *out_len, int32_t *row_status, int status_where, int flags,
+                                mrz_rs_report *rep) {
+    if (!ctx || !in || !out || !out_len || n < 0) return MRZ_E_ARG;
+    if (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
+    if (row_status && status_where != MRZ_MEM_HOST && status_where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
     const int64_t burst_in = (int64_t)MRZ_RS_K * MRZ_RS_ROWS, burst_out = (int64_t)MRZ_RS_N * MRZ_RS_ROWS;
     const int64_t nbursts = n / burst_out;
     const int64_t tail = n - nbursts * burst_out;
@@ -546,53 +709,88 @@ extern "C" int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where,
     const uint8_t *d_in = nullptr;
     int rc = mrz_stage_input(ctx, in, n, where, &d_in);
     if (rc) return rc;
-    if (!ctx->d_rs_tables) {
-        mrz_rs_tables *T = (mrz_rs_tables *)malloc(sizeof(mrz_rs_tables));
-        void *p = nullptr;
-        hipError_t e = T ? hipMalloc(&p, sizeof(mrz_rs_tables)) : hipErrorOutOfMemory;
-        if (e == hipSuccess) {
-            mrz_rs_build_tables(T);
-            e = hipMemcpy(p, T, sizeof(mrz_rs_tables), hipMemcpyHostToDevice);
-        }
-        free(T);
-        if (e != hipSuccess) {
-            ctx->last_err = e;
-            return MRZ_E_NOMEM;
-        }
-        ctx->d_rs_tables = p;
-    }
-    // device output: rows x 223 bytes, then one count per row
-    const int64_t rows = nbursts * MRZ_RS_ROWS;
-    rc = mrz_grow(ctx, &ctx->d_rs_out, &ctx->rs_out_cap, rows * MRZ_RS_K + rows * 4 + 16);
+    rc = mrz_rs_need_tables(ctx);
     if (rc) return rc;
-    uint8_t *d_out = ctx->d_rs_out;
-    int *d_counts = (int *)(d_out + ((rows * MRZ_RS_K + 15) / 16) * 16);
-    const int tiles = (MRZ_RS_ROWS + MRZ_RSD_ROWS - 1) / MRZ_RSD_ROWS;
-    hipLaunchKernelGGL(mrz_rs_decode_kernel, dim3((unsigned)(nbursts * tiles)), dim3(MRZ_RSD_ROWS), 0, ctx->stream, d_in,
-                       nbursts, (const mrz_rs_tables *)ctx->d_rs_tables, d_out, d_counts);
-    HIPCHK(ctx, hipGetLastError());
-    std::vector<int> counts((size_t)rows);
-    HIPCHK(ctx, hipMemcpyAsync(out_host, d_out, (size_t)(rows * MRZ_RS_K), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(counts.data(), d_counts, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    mrz_rs_report r;
-    memset(&r, 0, sizeof(r));
-    for (int64_t i = 0; i < rows; i++) {  // rs-mrzip.c:103-108
-        if (counts[(size_t)i] > 0) r.corrected += counts[(size_t)i];
-        if (counts[(size_t)i] == -1) r.uncorrectable++;
+    const int64_t rows = nbursts * MRZ_RS_ROWS, produced_all = rows * MRZ_RS_K;
+    uint8_t *d_out = (uint8_t *)out;
+    if (out_where == MRZ_MEM_HOST) {
+        rc = mrz_grow(ctx, &ctx->d_rs_out, &ctx->rs_out_cap, produced_all);
+        if (rc) return rc;
+        d_out = ctx->d_rs_out;
     }
-    int64_t produced = rows * MRZ_RS_K;
-    if (tail == 64 + 4) {
-        // trailer: BLAKE2b-512 of every 223-byte row as decoded, then the first short row and its length (:70-95)
-        uint8_t trailer[68], digest[64];
+    // scratch: totals and list length, one status per row (unless the caller's array is device memory), the list
+    const int64_t head_bytes = 64;
+    rc = mrz_grow(ctx, &ctx->d_rs_dec, &ctx->rs_dec_cap, head_bytes + rows * 4 + rows * (int64_t)sizeof(mrz_rsd_entry));
+    if (rc) return rc;
+    mrz_rsd_head *d_head = (mrz_rsd_head *)ctx->d_rs_dec;
+    int *d_counts = (int *)(ctx->d_rs_dec + head_bytes);
+    mrz_rsd_entry *d_list = (mrz_rsd_entry *)(ctx->d_rs_dec + head_bytes + rows * 4);
+    if (row_status && status_where == MRZ_MEM_DEVICE) d_counts = row_status;
+    int cus = 0;
+    HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    if (cus < 1) cus = 1;
+
+    const bool has_trailer = tail == 64 + 4, hash = has_trailer && !(flags & MRZ_RS_SKIP_CHECKSUM);
+    uint8_t trailer[68];
+    mrz_rsd_head h_head;
+    std::vector<uint8_t> hash_copy;  // device output: the rows come to the host to be hashed
+    if (hash && out_where == MRZ_MEM_DEVICE) hash_copy.resize((size_t)produced_all);
+    hipError_t e = hipMemsetAsync(d_head, 0, sizeof(mrz_rsd_head), ctx->stream);
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (ctx->profiling) {
+        hipEventCreate(&ea);
+        hipEventCreate(&eb);
+        hipEventRecord(ea, ctx->stream);
+    }
+    if (e == hipSuccess) {
+        const int tiles = (MRZ_RS_ROWS + MRZ_RSD_ROWS - 1) / MRZ_RSD_ROWS;
+        hipLaunchKernelGGL(mrz_rs_decode_kernel, dim3((unsigned)(nbursts * tiles)), dim3(MRZ_RSD_ROWS), 0, ctx->stream, d_in,
+                           (const mrz_rs_tables *)ctx->d_rs_tables, d_out, d_counts, d_head, d_list);
+        hipLaunchKernelGGL(mrz_rs_repair_kernel, dim3((unsigned)(cus * MRZ_RSR_WGS_PER_CU)), dim3(MRZ_RSR_THREADS), 0,
+                           ctx->stream, (const mrz_rs_tables *)ctx->d_rs_tables, (const mrz_rsd_entry *)d_list, d_head, d_out,
+                           d_counts);
+        e = hipGetLastError();
+    }
+    if (ctx->profiling) hipEventRecord(eb, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_head, d_head, sizeof(h_head), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && out_where == MRZ_MEM_HOST)
+        e = hipMemcpyAsync(out, d_out, (size_t)produced_all, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && hash && out_where == MRZ_MEM_DEVICE)
+        e = hipMemcpyAsync(hash_copy.data(), d_out, (size_t)produced_all, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && row_status && status_where == MRZ_MEM_HOST)
+        e = hipMemcpyAsync(row_status, d_counts, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && has_trailer) {
         if (where == MRZ_MEM_HOST)
             memcpy(trailer, (const uint8_t *)in + nbursts * burst_out, 68);
         else
-            HIPCHK(ctx, hipMemcpy(trailer, (const uint8_t *)in + nbursts * burst_out, 68, hipMemcpyDeviceToHost));
-        HostB2 b;
-        b.update((const uint8_t *)out_host, (size_t)produced);
-        b.final(digest);
-        r.checksum_ok = memcmp(digest, trailer, 64) == 0;
+            e = hipMemcpyAsync(trailer, (const uint8_t *)in + nbursts * burst_out, 68, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t e_sync = hipStreamSynchronize(ctx->stream);  // the call's one wait
+    if (e == hipSuccess) e = e_sync;
+    if (ctx->profiling) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ea, eb) == hipSuccess) ctx->timings.encode_ms = ms;  // reported via mrz_get_timings
+        hipEventDestroy(ea);
+        hipEventDestroy(eb);
+    }
+    if (e != hipSuccess) {
+        ctx->last_err = e;
+        return MRZ_E_HIP;
+    }
+    mrz_rs_report r;
+    memset(&r, 0, sizeof(r));
+    r.corrected = (int64_t)h_head.corrected;  // rs-mrzip.c:103-108
+    r.uncorrectable = (int64_t)h_head.uncorrectable;
+    int64_t produced = produced_all;
+    if (has_trailer) {
+        // trailer: BLAKE2b-512 of every 223-byte row as decoded, then the first short row and its length (:70-95)
+        if (hash) {
+            uint8_t digest[64];
+            HostB2 b;
+            b.update(out_where == MRZ_MEM_HOST ? (const uint8_t *)out : hash_copy.data(), (size_t)produced_all);
+            b.final(digest);
+            r.checksum_ok = memcmp(digest, trailer, 64) == 0;
+        }
         const int64_t k_i = trailer[64] | trailer[65] << 8, k_j = trailer[66] | trailer[67] << 8;
         if (k_i < MRZ_RS_ROWS) {
             const int64_t cut = (nbursts - 1) * burst_in + k_i * MRZ_RS_K + (k_j < MRZ_RS_K ? k_j : MRZ_RS_K);
@@ -600,7 +798,13 @@ extern "C" int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where,
         }
     } else
         r.truncated = 1;  // "file truncated. can't validate the checksum or remove superfluous 0x00 padding" (:58-68)
+    if (flags & MRZ_RS_SKIP_CHECKSUM) r.checksum_ok = -1;
     *out_len = produced;
     if (rep) *rep = r;
     return MRZ_OK;
+}
+
+extern "C" int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out_host, int64_t out_cap,
+                             int64_t *out_len, mrz_rs_report *rep) {
+    return mrz_rs_decode_ex(ctx, in, n, where, out_host, MRZ_MEM_HOST, out_cap, out_len, nullptr, MRZ_MEM_HOST, 0, rep);
 }
