@@ -1002,7 +1002,8 @@ int mrzo_decompress(const uint8_t *mrz, int64_t n, mrzo_buf *out) {
                 }
                 int64_t dist = peek_le(s0.p + i, cb);
                 i += cb;
-                if (dist < 1 || dist > out->len || buf_reserve(out, len)) {
+                /* n = MIN(len, offset) < 1 is "corrupt archive" (:175-176): an empty match is one too */
+                if (len < 1 || dist < 1 || dist > out->len || buf_reserve(out, len)) {
                     rc = -5;
                     break;
                 }
