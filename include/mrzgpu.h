@@ -324,6 +324,34 @@ int64_t mrz_rs_codewords(int64_t n); /* (n / 2084880) * 8176; 0 when n holds no 
 int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where, int64_t out_cap,
                      int64_t *out_len, int32_t *row_status, int status_where, int flags, mrz_rs_report *rep);
 
+/* mrz_rs_decode_ex for a caller who knows where the damage is (an unreadable sector list, a ddrescue map, a zero-filled
+ * hole, a file padded back to its length): the lost bytes become erasures, and RS(255,223) corrects any mix of e
+ * erasures and t unknown errors per codeword with e + 2 t <= 32 -- a contiguous lost run of 32 x 8176 bytes per burst
+ * instead of 16 x 8176.  Every argument but lost / n_lost means what it means for mrz_rs_decode_ex.
+ *   lost / n_lost     n_lost byte ranges [offset, offset + len) of the ENCODED input `in`, in HOST memory: every len > 0,
+ *                     offset >= 0, offset + len <= n, ascending by offset and disjoint (adjacent ranges are allowed);
+ *                     anything else is MRZ_E_ARG.  The bytes inside a range may hold anything (zeros, garbage, the
+ *                     right value).  What a range covers beyond the last whole burst (trailer, partial burst) is
+ *                     ignored.  n_lost == 0 (lost may be NULL) is mrz_rs_decode_ex exactly.
+ * Column c of row r of burst b is erased if byte b * 2084880 + c * 8176 + r lies in a lost range; the parity columns
+ * 223..254 count like any other.  Per codeword:
+ *   - syndromes all zero: status 0, whatever is marked (rsd32 returns before it looks at eras_pos);
+ *   - otherwise, with 0..32 erased columns: bytes and status are those of rsd32(row, eras_pos = those columns, no_eras),
+ *     miscorrections included.  The status is the number of roots of the errata locator: erased columns are counted
+ *     even where the byte turned out to be right (5 erased but intact columns and 1 real error give 6);
+ *   - more than 32 erased columns and non-zero syndromes: status -1, the row is left as it came.  The reference has no
+ *     behaviour there (its locator loop would write lambda[33]); this is this library's definition.
+ * rep->corrected is the sum of the positive statuses, rep->uncorrectable the number of -1, as in mrz_rs_decode_ex;
+ * checksum, trailer and truncation are handled alike.  The ranges are copied to the device on the ctx stream (16 bytes
+ * each); undamaged codewords never look at them, a damaged one searches them in O(log n_lost). */
+typedef struct {
+    int64_t offset;
+    int64_t len;
+} mrz_rs_range;
+int mrz_rs_decode_lost(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where, int64_t out_cap,
+                       int64_t *out_len, const mrz_rs_range *lost, int64_t n_lost, int32_t *row_status, int status_where,
+                       int flags, mrz_rs_report *rep);
+
 /* ---- runzip: decoder of the two rzip streams of a chunk ---------- */
 
 /* Replaces the record loop of runzip_chunk (src/runzip.c:277-308) with unzip_literal (:120-157) and

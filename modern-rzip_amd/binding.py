@@ -46,6 +46,11 @@ class RsReport(ctypes.Structure):
                 ("truncated", ctypes.c_int32)]
 
 
+class RsRange(ctypes.Structure):
+    """mrz_rs_range: bytes [offset, offset + len) of an encoded input"""
+    _fields_ = [("offset", ctypes.c_int64), ("len", ctypes.c_int64)]
+
+
 class Control(ctypes.Structure):
     """The rzip_control fields rzip_fd reads for `mrzip -n` (include/mrzgpu_host.h)."""
     _fields_ = [("rzip_compression_level", ctypes.c_int), ("compression_level", ctypes.c_int),
@@ -103,6 +108,9 @@ def load_library(path=None):
         lib.mrz_rs_codewords.restype = i64
         lib.mrz_rs_decode_ex.argtypes = [vp, vp, i64, ci, vp, ci, i64, ctypes.POINTER(i64), vp, ci, ci,
                                          ctypes.POINTER(RsReport)]
+    if hasattr(lib, "mrz_rs_decode_lost"):
+        lib.mrz_rs_decode_lost.argtypes = [vp, vp, i64, ci, vp, ci, i64, ctypes.POINTER(i64), ctypes.POINTER(RsRange), i64,
+                                           vp, ci, ci, ctypes.POINTER(RsReport)]
     if hasattr(lib, "mrz_window_scan"):
         i64p = ctypes.POINTER(i64)
         lib.mrz_window_scan.argtypes = [vp, vp, i64, ci, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, ci, i64p, i64p]
@@ -488,9 +496,19 @@ class RzipContext:
         -1 uncorrectable) as a numpy array; a cuda int32 tensor or a (device pointer, nbytes) pair = filled on the
         device and returned as it is; False/None = not asked for.  With `out` = a cuda tensor or a (device pointer,
         nbytes) pair the bytes stay on the device and the report gains out_len."""
+        return self._rs_decode("rs_decode_ex", data, None, out, status, skip_checksum)
+
+    def rs_decode_lost(self, data, lost, out=None, status=True, skip_checksum=False):
+        """mrz_rs_decode_lost: rs_decode_ex told which bytes of `data` were lost.  lost: a sequence of (offset, len),
+        byte ranges of the encoded input, ascending and disjoint; their columns are erasures, and a codeword is restored
+        from any e erasures and t errors with e + 2 t <= 32.  The status counts erased columns too; more than 32 in a
+        damaged codeword give -1.  Everything else, and what comes back, as in rs_decode_ex."""
+        return self._rs_decode("rs_decode_lost", data, lost, out, status, skip_checksum)
+
+    def _rs_decode(self, name, data, lost, out, status, skip_checksum):
         import numpy as np
-        if not hasattr(self.lib, "mrz_rs_decode_ex"):
-            raise MrzError("this libmrzgpu has no mrz_rs_decode_ex: rebuild it")
+        if not hasattr(self.lib, "mrz_" + name):
+            raise MrzError("this libmrzgpu has no mrz_%s: rebuild it" % name)
         ptr, n, where, keep = _as_ptr(data)
         cap = (n // 2084880) * 1823248
         rows = self.lib.mrz_rs_codewords(n)
@@ -501,7 +519,7 @@ class RzipContext:
         elif status is not None and status is not False:
             st_ptr, st_n, st_where, st_keep = _as_ptr(status)
             if st_where != MEM_DEVICE or st_n < rows * 4:
-                raise MrzError("rs_decode_ex: status must be device memory of 4 bytes per codeword")
+                raise MrzError(name + ": status must be device memory of 4 bytes per codeword")
             st_arr = status
         out_len = ctypes.c_int64()
         rep = RsReport()
@@ -512,9 +530,16 @@ class RzipContext:
         else:
             po, no, wo, ko = _as_ptr(out)
             if wo != MEM_DEVICE:
-                raise MrzError("rs_decode_ex: out must be device memory (leave it out for bytes)")
-        _check(self.lib, self.lib.mrz_rs_decode_ex(self.ctx, ptr, n, where, po, wo, no, ctypes.byref(out_len), st_ptr,
-                                                   st_where, flags, ctypes.byref(rep)), self.ctx)
+                raise MrzError(name + ": out must be device memory (leave it out for bytes)")
+        if lost is None:
+            rc = self.lib.mrz_rs_decode_ex(self.ctx, ptr, n, where, po, wo, no, ctypes.byref(out_len), st_ptr, st_where,
+                                           flags, ctypes.byref(rep))
+        else:
+            lost = list(lost)
+            ranges = (RsRange * max(len(lost), 1))(*[RsRange(int(o), int(ln)) for o, ln in lost])
+            rc = self.lib.mrz_rs_decode_lost(self.ctx, ptr, n, where, po, wo, no, ctypes.byref(out_len), ranges, len(lost),
+                                             st_ptr, st_where, flags, ctypes.byref(rep))
+        _check(self.lib, rc, self.ctx)
         report = dict(corrected=rep.corrected, uncorrectable=rep.uncorrectable,
                       checksum_ok=-1 if rep.checksum_ok < 0 else bool(rep.checksum_ok), truncated=bool(rep.truncated))
         if out is None:

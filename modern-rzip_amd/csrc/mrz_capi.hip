@@ -118,6 +118,7 @@ extern "C" void mrz_close(mrz_ctx *ctx) {
     if (ctx->d_rs_tables) hipFree(ctx->d_rs_tables);
     if (ctx->d_rs_out) hipFree(ctx->d_rs_out);
     if (ctx->d_rs_dec) hipFree(ctx->d_rs_dec);
+    if (ctx->d_rs_lost) hipFree(ctx->d_rs_lost);
     if (ctx->lz4_scratch) hipFree(ctx->lz4_scratch);
     if (ctx->b2_scratch) hipFree(ctx->b2_scratch);
     if (ctx->side_stream) hipStreamDestroy(ctx->side_stream);

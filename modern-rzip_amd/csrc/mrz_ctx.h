@@ -74,6 +74,8 @@ struct mrz_ctx {
     int64_t rs_out_cap;
     uint8_t *d_rs_dec;  // decoder scratch: totals, row statuses, the list of damaged rows
     int64_t rs_dec_cap;
+    mrz_rs_range *d_rs_lost;  // the lost ranges of the mrz_rs_decode_lost call in flight
+    int64_t rs_lost_cap;
     void *rz_scratch;  // runzip: parse tables, records, staged streams (mrz_runzip.hip)
     int64_t rz_scratch_cap;
     uint8_t *d_rz_out;

@@ -423,6 +423,21 @@ extern "C" int mrz_rs_encode(mrz_ctx *ctx, const void *in, int64_t n, int where,
 // 223..254 are parity: counted, not part of the output.  A locator with deg distinct roots is separable, so its
 // derivative cannot vanish at one of them (rsd32's `den == 0` exit is dead code once the root count matches); a guard
 // reports -1 all the same.  Roots are distinct columns, so the order they are applied in does not matter.
+//
+// Known-lost ranges (mrz_rs_decode_lost, mrz_rs_repair_kernel<true>): rsd32(data, eras_pos, no_eras), :183-193,198-221,
+// which the reference's decode() always calls with no_eras = 0.  The caller's sorted byte ranges of the encoded input
+// are copied to device scratch on the ctx stream; mrz_rs_decode_kernel does not look at them (clean input pays
+// nothing), and the repair kernel without them, <false>, is the kernel above.  Per listed codeword <true> adds:
+//   * every lane searches the ranges for the byte offsets of the columns of its four Chien points (binary search);
+//     four ballots give the erased columns in the Chien layout, no_eras is their popcount;
+//   * lambda starts as the erasure locator prod (1 + alpha^(11 c) x): no_eras wave-uniform steps
+//     lam_i ^= alpha^u lam_(i-1) through the two slots of b in turn, then b_i = log lam_i;
+//   * Berlekamp-Massey runs from r = no_eras + 1 with el = no_eras, the branch test 2 el <= r + no_eras - 1 and the
+//     update el = r + no_eras - el: 32 - no_eras steps.  Chien, omega and Forney are unchanged; deg may reach 32.
+// Three rules fix the status: zero syndromes give 0 whatever is marked (the row is never listed; rsd32 returns before
+// it looks at eras_pos); more than 32 erased columns in a listed row give -1 and the row stays as it came (this
+// project's definition: rsd32's locator loop would write lambda[33]); otherwise the status is rsd32's, the number of
+// roots of the errata locator, in which erased columns count even where the byte was right.
 #define MRZ_RSD_ROWS 128
 #define MRZ_RSD_STRIDE 260  // bytes per LDS row (65 words: lanes of a wave hit different banks)
 #define MRZ_RSR_THREADS 256  // repair kernel: 4 waves per workgroup
@@ -535,10 +550,28 @@ struct mrz_rsr_wave {
     uint8_t om[32];       // omega in index form
 };
 
+// is byte `pos` of the encoded input inside one of the n sorted, disjoint ranges?  (the last range that starts at or
+// before pos is the only one that can hold it)
+__device__ static inline bool mrz_rs_in_ranges(const mrz_rs_range *__restrict__ rg, int64_t n, int64_t pos) {
+    int64_t lo = 0, hi = n;  // -> the first range that starts beyond pos
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (rg[mid].offset <= pos)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo > 0 && pos < rg[lo - 1].offset + rg[lo - 1].len;
+}
+
+// ERAS = false is the decoder without erasures (mrz_rs_decode_ex; rg / n_rg are not looked at); ERAS = true takes the
+// caller's lost ranges (mrz_rs_decode_lost).
+template <bool ERAS>
 __global__ __launch_bounds__(MRZ_RSR_THREADS) void mrz_rs_repair_kernel(const mrz_rs_tables *__restrict__ T,
                                                                         const mrz_rsd_entry *__restrict__ list,
                                                                         mrz_rsd_head *__restrict__ head,
-                                                                        uint8_t *__restrict__ out, int *__restrict__ counts) {
+                                                                        uint8_t *__restrict__ out, int *__restrict__ counts,
+                                                                        const mrz_rs_range *__restrict__ rg, int64_t n_rg) {
     __shared__ uint8_t s_ex[512];  // alpha^i for i = 0..509: the sum of two index forms needs no reduction mod 255
     __shared__ uint8_t s_lg[256], s_tal[256];
     __shared__ __attribute__((aligned(16))) mrz_rsr_wave s_wave[MRZ_RSR_THREADS / 64];
@@ -564,13 +597,51 @@ __global__ __launch_bounds__(MRZ_RSR_THREADS) void mrz_rs_repair_kernel(const mr
     for (unsigned k = blockIdx.x * (MRZ_RSR_THREADS / 64) + tid / 64; k < n_listed; k += n_waves) {
         const mrz_rsd_entry *ent = &list[k];
         const int row = ent->row;
+        // the erased columns, in the layout of the Chien points: bit l of eras[p] = column 139 pt mod 255 of point
+        // pt = l + 1 + 64 p lies in a lost range (column c of row r of burst b is byte b * 2084880 + c * 8176 + r)
+        unsigned long long eras[4] = { 0, 0, 0, 0 };
+        int no_eras = 0;
+        if (ERAS) {
+            const int64_t at = (int64_t)(row / MRZ_RS_ROWS) * ((int64_t)MRZ_RS_N * MRZ_RS_ROWS) + row % MRZ_RS_ROWS;
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const int col = (139 * pt[p]) % 255;
+                eras[p] = __ballot(pt[p] <= 255 && mrz_rs_in_ranges(rg, n_rg, at + (int64_t)col * MRZ_RS_ROWS));
+                no_eras += __popcll(eras[p]);
+            }
+            if (no_eras > 32) {  // beyond the code's reach (and rsd32's lambda[33]): uncorrectable, the row stays as it came
+                if (lane == 0) counts[row] = -1;
+                lost++;
+                continue;
+            }
+        }
         W->syn[lane] = lane >= 1 && lane <= 32 ? reinterpret_cast<const uint8_t *>(ent->s)[lane - 1] : (uint8_t)255;
 
         // Berlekamp-Massey: lambda in polynomial form, b in index form, coefficient i on lane i (0..32)
         int lam = lane == 0 ? 1 : 0, b = lane == 0 ? 0 : 255, el = 0;
         (void)__ballot(1);  // syn is there
+        if (ERAS && no_eras) {
+            // lambda starts as the erasure locator prod (1 + alpha^(11 c) x) over the erased columns c (:183-193): one
+            // wave-uniform step lam_i ^= alpha^u lam_(i-1) per column, the coefficient below handed down through the
+            // slots of b (b[.][0] = 255 is the zero that lane 0 takes).  The product does not depend on the order.
+            int k = 0;
 #pragma unroll 1
-        for (int r = 1; r <= 32; r++) {
+            for (int p = 0; p < 4; p++) {
+#pragma unroll 1
+                for (unsigned long long m = eras[p]; m; m &= m - 1) {
+                    const int c = (139 * (__ffsll((long long)m) + 64 * p)) % 255, u = (11 * c) % 255;
+                    const int slot = ++k & 1;
+                    if (lane <= 32) W->b[slot][lane + 1] = s_lg[lam];
+                    (void)__ballot(1);
+                    const int down = lane <= 32 ? (int)W->b[slot][lane] : 255;
+                    if (down != 255) lam ^= s_ex[u + down];
+                }
+            }
+            b = s_lg[lam];
+            el = no_eras;
+        }
+#pragma unroll 1
+        for (int r = no_eras + 1; r <= 32; r++) {
             const int slot = r & 1;
             if (lane < 32) {
                 int t = 0;
@@ -592,8 +663,8 @@ __global__ __launch_bounds__(MRZ_RSR_THREADS) void mrz_rs_repair_kernel(const mr
                 b = bdown;
             } else {
                 const int t = bdown != 255 ? lam ^ (int)s_ex[d + bdown] : lam;
-                if (2 * el <= r - 1) {
-                    el = r - el;
+                if (2 * el <= r + no_eras - 1) {
+                    el = r + no_eras - el;
                     const int q = (int)s_lg[lam] - d + 255;
                     b = lam == 0 ? 255 : (q >= 255 ? q - 255 : q);
                 } else
@@ -694,9 +765,10 @@ extern "C" int64_t mrz_rs_codewords(int64_t n) {
     return n < 0 ? 0 : n / ((int64_t)MRZ_RS_N * MRZ_RS_ROWS) * MRZ_RS_ROWS;
 }
 
-extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where,
-                                int64_t out_cap, int64_t *out_len, int32_t *row_status, int status_where, int flags,
-                                mrz_rs_report *rep) {
+// mrz_rs_decode_ex (n_lost = 0) and mrz_rs_decode_lost: `lost` is host memory, checked by the caller
+static int mrz_rs_decode_impl(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where,
+                              int64_t out_cap, int64_t *out_len, const mrz_rs_range *lost, int64_t n_lost,
+                              int32_t *row_status, int status_where, int flags, mrz_rs_report *rep) {
     if (!ctx || !in || !out || !out_len || n < 0) return MRZ_E_ARG;
     if (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
     if (row_status && status_where != MRZ_MEM_HOST && status_where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
@@ -726,6 +798,10 @@ extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int whe
     int *d_counts = (int *)(ctx->d_rs_dec + head_bytes);
     mrz_rsd_entry *d_list = (mrz_rsd_entry *)(ctx->d_rs_dec + head_bytes + rows * 4);
     if (row_status && status_where == MRZ_MEM_DEVICE) d_counts = row_status;
+    if (n_lost > 0) {  // the sorted ranges, for the repair kernel's search
+        rc = mrz_grow(ctx, &ctx->d_rs_lost, &ctx->rs_lost_cap, n_lost);
+        if (rc) return rc;
+    }
     int cus = 0;
     HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     if (cus < 1) cus = 1;
@@ -736,6 +812,8 @@ extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int whe
     std::vector<uint8_t> hash_copy;  // device output: the rows come to the host to be hashed
     if (hash && out_where == MRZ_MEM_DEVICE) hash_copy.resize((size_t)produced_all);
     hipError_t e = hipMemsetAsync(d_head, 0, sizeof(mrz_rsd_head), ctx->stream);
+    if (e == hipSuccess && n_lost > 0)
+        e = hipMemcpyAsync(ctx->d_rs_lost, lost, (size_t)n_lost * sizeof(mrz_rs_range), hipMemcpyHostToDevice, ctx->stream);
     hipEvent_t ea = nullptr, eb = nullptr;
     if (ctx->profiling) {
         hipEventCreate(&ea);
@@ -746,9 +824,14 @@ extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int whe
         const int tiles = (MRZ_RS_ROWS + MRZ_RSD_ROWS - 1) / MRZ_RSD_ROWS;
         hipLaunchKernelGGL(mrz_rs_decode_kernel, dim3((unsigned)(nbursts * tiles)), dim3(MRZ_RSD_ROWS), 0, ctx->stream, d_in,
                            (const mrz_rs_tables *)ctx->d_rs_tables, d_out, d_counts, d_head, d_list);
-        hipLaunchKernelGGL(mrz_rs_repair_kernel, dim3((unsigned)(cus * MRZ_RSR_WGS_PER_CU)), dim3(MRZ_RSR_THREADS), 0,
-                           ctx->stream, (const mrz_rs_tables *)ctx->d_rs_tables, (const mrz_rsd_entry *)d_list, d_head, d_out,
-                           d_counts);
+        if (n_lost > 0)
+            hipLaunchKernelGGL(mrz_rs_repair_kernel<true>, dim3((unsigned)(cus * MRZ_RSR_WGS_PER_CU)), dim3(MRZ_RSR_THREADS),
+                               0, ctx->stream, (const mrz_rs_tables *)ctx->d_rs_tables, (const mrz_rsd_entry *)d_list, d_head,
+                               d_out, d_counts, (const mrz_rs_range *)ctx->d_rs_lost, n_lost);
+        else
+            hipLaunchKernelGGL(mrz_rs_repair_kernel<false>, dim3((unsigned)(cus * MRZ_RSR_WGS_PER_CU)), dim3(MRZ_RSR_THREADS),
+                               0, ctx->stream, (const mrz_rs_tables *)ctx->d_rs_tables, (const mrz_rsd_entry *)d_list, d_head,
+                               d_out, d_counts, (const mrz_rs_range *)nullptr, (int64_t)0);
         e = hipGetLastError();
     }
     if (ctx->profiling) hipEventRecord(eb, ctx->stream);
@@ -802,6 +885,26 @@ extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int whe
     *out_len = produced;
     if (rep) *rep = r;
     return MRZ_OK;
+}
+
+extern "C" int mrz_rs_decode_ex(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where,
+                                int64_t out_cap, int64_t *out_len, int32_t *row_status, int status_where, int flags,
+                                mrz_rs_report *rep) {
+    return mrz_rs_decode_impl(ctx, in, n, where, out, out_where, out_cap, out_len, nullptr, 0, row_status, status_where,
+                              flags, rep);
+}
+
+extern "C" int mrz_rs_decode_lost(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out, int out_where,
+                                  int64_t out_cap, int64_t *out_len, const mrz_rs_range *lost, int64_t n_lost,
+                                  int32_t *row_status, int status_where, int flags, mrz_rs_report *rep) {
+    if (n_lost < 0 || (n_lost > 0 && !lost) || n < 0) return MRZ_E_ARG;
+    int64_t end = 0;  // of the range before: ascending and disjoint (adjacent is allowed)
+    for (int64_t i = 0; i < n_lost; i++) {
+        if (lost[i].len <= 0 || lost[i].offset < end || lost[i].len > n - lost[i].offset) return MRZ_E_ARG;
+        end = lost[i].offset + lost[i].len;
+    }
+    return mrz_rs_decode_impl(ctx, in, n, where, out, out_where, out_cap, out_len, lost, n_lost, row_status, status_where,
+                              flags, rep);
 }
 
 extern "C" int mrz_rs_decode(mrz_ctx *ctx, const void *in, int64_t n, int where, void *out_host, int64_t out_cap,

@@ -1,10 +1,13 @@
-"""Device time of the RS(255,223) decoder (device in, device out, checksum skipped) on three damage profiles:
+"""Device time of the RS(255,223) decoder (device in, device out, checksum skipped) on four damage profiles:
     clean      nothing damaged: every codeword ends with its syndromes
     scattered  1 % of the codewords, 1..16 byte errors each
     burst      in every 8th burst a contiguous run of 16 x 8176 damaged bytes: 16 errors in each of its codewords
+    lost-run   in every 8th burst a zero-filled run of 32 x 8176 bytes, declared lost (mrz_rs_decode_lost): 32 erasures
+               in each of its codewords.  A library without mrz_rs_decode_lost is not run on it.
 usage: probe_rs_decode.py [lib.so [parent.so]] [GiB]
 One JSON line per library and profile: the median of 5 timed runs after a warm-up.  timings_ms is what the library
-reports (mrz_timings.encode_ms); kernel_ms is the sum of its decode kernels' durations as torch.profiler sees them,
+reports (mrz_timings.encode_ms); kernel_ms is the sum of its decode kernels' durations as torch.profiler sees them
+(repair_ms: the repair kernel's share of it),
 which also works for a library without mrz_rs_decode_ex (a build of an earlier commit: it is called through
 mrz_rs_decode with device input, and its copy to the host and its hash are not part of kernel_ms).  With a second
 library both must produce the same bytes and totals, and a line with the ratio new / parent follows for every profile."""
@@ -44,17 +47,26 @@ def damage(enc, nbursts, kind, gen):
     elif kind == "burst":
         for b in range(0, nbursts, 8):
             enc[b * BURST + 5000:b * BURST + 5000 + 16 * ROWS] ^= 0xa5
+    elif kind == "lost-run":
+        for off, n in lost_runs(nbursts):
+            enc[off:off + n] = 0
     return enc
 
 
+def lost_runs(nbursts):
+    """the (offset, len) ranges of the lost-run profile"""
+    return [(b * BURST + 5000, 32 * ROWS) for b in range(0, nbursts, 8)]
+
+
 def kernel_ms(fn):
-    """device time of the rs decode kernels that fn() launches, by the profiler; None if it saw none"""
+    """device time of the rs decode kernels that fn() launches and of the repair kernel among them, by the profiler;
+    (None, None) if it saw none"""
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         fn()
         torch.cuda.synchronize()
-    us = [getattr(e, "device_time_total", 0) or getattr(e, "cuda_time_total", 0) for e in prof.events()
-          if "mrz_rs_decode_kernel" in e.name or "mrz_rs_repair_kernel" in e.name]
-    return sum(us) / 1e3 if us else None
+    us = [(getattr(e, "device_time_total", 0) or getattr(e, "cuda_time_total", 0), "mrz_rs_repair_kernel" in e.name)
+          for e in prof.events() if "mrz_rs_decode_kernel" in e.name or "mrz_rs_repair_kernel" in e.name]
+    return (sum(u for u, _ in us) / 1e3, sum(u for u, rep in us if rep) / 1e3) if us else (None, None)
 
 
 def main():
@@ -77,9 +89,14 @@ def main():
     cap = nbursts * ROWS * K
     d_out = torch.empty(cap, dtype=torch.uint8, device="cuda")
     medians = {}
-    for kind in ("clean", "scattered", "burst"):
+    for kind in ("clean", "scattered", "burst", "lost-run"):
         enc = damage(clean, nbursts, kind, gen)
+        runs_lost = lost_runs(nbursts)
+        ranges = (m.binding.RsRange * len(runs_lost))(*[m.binding.RsRange(o, ln) for o, ln in runs_lost])
         for name, lib in named:
+            if kind == "lost-run" and not hasattr(lib, "mrz_rs_decode_lost"):
+                print(json.dumps(dict(lib=name, profile=kind, note="this library has no mrz_rs_decode_lost")), flush=True)
+                continue
             ex = hasattr(lib, "mrz_rs_decode_ex")
             host_out = None if ex else ctypes.create_string_buffer(cap)
             with m.RzipContext(lib=lib) as ctx:
@@ -87,7 +104,11 @@ def main():
                 out_len, rep = ctypes.c_int64(), m.binding.RsReport()
 
                 def call():
-                    if ex:
+                    if kind == "lost-run":
+                        rc = lib.mrz_rs_decode_lost(ctx.ctx, ctypes.c_void_p(enc.data_ptr()), total, 1,
+                                                    ctypes.c_void_p(d_out.data_ptr()), 1, cap, ctypes.byref(out_len), ranges,
+                                                    len(runs_lost), None, 0, 1, ctypes.byref(rep))
+                    elif ex:
                         rc = lib.mrz_rs_decode_ex(ctx.ctx, ctypes.c_void_p(enc.data_ptr()), total, 1,
                                                   ctypes.c_void_p(d_out.data_ptr()), 1, cap, ctypes.byref(out_len), None, 0,
                                                   1, ctypes.byref(rep))
@@ -100,8 +121,8 @@ def main():
                 runs = []
                 for _ in range(RUNS):
                     t0 = time.perf_counter()
-                    k_ms = kernel_ms(call)
-                    runs.append(dict(kernel_ms=k_ms, call_ms=(time.perf_counter() - t0) * 1e3,
+                    k_ms, r_ms = kernel_ms(call)
+                    runs.append(dict(kernel_ms=k_ms, repair_ms=r_ms, call_ms=(time.perf_counter() - t0) * 1e3,
                                      timings_ms=ctx.timings().encode_ms if ex else None))
                 produced = d_out.cpu().numpy().data if ex else memoryview(host_out).cast("B")
                 digest = hashlib.blake2b(produced[:out_len.value], digest_size=8).hexdigest()
@@ -112,13 +133,14 @@ def main():
                         kernel_ms_runs=[round(v, 3) for v in k] if measured else None,
                         kernel_ms_median=round(statistics.median(k), 3) if measured else None,
                         kernel_ms_spread=round(max(k) - min(k), 3) if measured else None,
+                        repair_ms_median=round(statistics.median(r["repair_ms"] for r in runs), 3) if measured else None,
                         timings_ms_median=round(statistics.median(r["timings_ms"] for r in runs), 3) if ex else None,
                         call_ms_median=round(statistics.median(r["call_ms"] for r in runs), 1))
             if measured:
                 line["input_GBps"] = round(total / line["kernel_ms_median"] / 1e6, 1)
             medians[(name, kind)] = line
             print(json.dumps(line), flush=True)
-        if len(named) > 1:
+        if len(named) > 1 and ("parent", kind) in medians:
             a, b = medians[("new", kind)], medians[("parent", kind)]
             assert all(a[f] == b[f] for f in ("corrected", "uncorrectable", "out_len", "out_blake2b")), (a, b)
             if a["kernel_ms_median"] is not None and b["kernel_ms_median"] is not None:
