@@ -368,6 +368,44 @@ int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s
                      int chunk_bytes, void *out, int out_where, int64_t out_cap, int64_t *out_len, uint32_t *crc_calc,
                      uint32_t *crc_stored);
 
+/* Range decode: bytes [first, first + count) of the chunk without decoding the chunk.  After the same three parse
+ * launches as mrz_runzip_chunk every record's output position is known; each output byte then has exactly one origin
+ * in stream 1, reached by following match records backwards (a match sends a position to
+ * out_pos - dist + (position - out_pos) % min(len, dist), src/runzip.c:182-199).  That walk is independent per byte:
+ * no output buffer of the chunk's size, and no literal byte is read that is not delivered.
+ *
+ * Both functions parse and validate the WHOLE of stream 0, whatever the range, and give MRZ_E_CORRUPT for exactly
+ * the streams mrz_runzip_chunk refuses (s1_len is needed for that: literals beyond stream 1).  Once the parse has
+ * succeeded info->chunk_len is set (info may be NULL); first < 0, count < 0 or first + count > chunk_len then give
+ * MRZ_E_ARG.  count == 0 is MRZ_OK, writes nothing and takes out == NULL: the sizing call.  Otherwise exactly
+ * `count` bytes (mrz_runzip_range) or `count` int64 (mrz_runzip_origins; device memory must be 8-byte aligned) are
+ * written, nothing outside them.
+ *
+ * NO CRC is computed or compared: the CRC stored behind the terminator covers the whole chunk.  A caller that needs
+ * the check decodes the chunk with mrz_runzip_chunk.
+ *
+ * Cost follows info->total_hops (match records followed, summed over the bytes of the range), each hop a binary
+ * search over the records, not the size of the chunk.  Where matches copy matches many times over -- a period repeated
+ * through the chunk: the depth is the position divided by the period -- a range can cost more than the whole decode.
+ * Device scratch grows with s0_len and count, never with chunk_len.
+ *
+ *   mrz_runzip_origins  origins[i] = offset in stream 1 of output byte first + i.  Stream 1 itself is not needed:
+ *                       a caller whose literals live in a file or in archive blocks fetches the bytes from there.
+ *                       `where` says where s0 is, out_where where `origins` is.
+ *   mrz_runzip_range    where == MRZ_MEM_DEVICE: the kernel reads stream 1 in place.  where == MRZ_MEM_HOST: stream 0
+ *                       is uploaded, stream 1 is NOT; the origins are resolved on the device and the bytes gathered
+ *                       on the host, in runs of consecutive origins.
+ * Both may be mixed freely with mrz_runzip_chunk on one context (they share its scratch). */
+typedef struct {
+    int64_t chunk_len;   /* bytes the whole chunk decodes to */
+    int64_t total_hops;  /* match records followed, summed over the bytes of the range */
+    int64_t max_hops;    /* the most for one byte */
+} mrz_range_info;
+int mrz_runzip_range(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
+                     int chunk_bytes, int64_t first, int64_t count, void *out, int out_where, mrz_range_info *info);
+int mrz_runzip_origins(mrz_ctx *ctx, const void *s0, int64_t s0_len, int64_t s1_len, int where, int chunk_bytes,
+                       int64_t first, int64_t count, int64_t *origins, int out_where, mrz_range_info *info);
+
 #ifdef __cplusplus
 }
 #endif

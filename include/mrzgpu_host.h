@@ -99,6 +99,18 @@ int mrz_rzip_pipeline(const mrz_control *control, const void *in, int64_t n, mrz
  * *out is malloc'd by the library (mrz_free).  Record decoding runs on the GPU (mrz_runzip_chunk). */
 int mrz_runzip_buffer(int device, const void *mrz, int64_t n, void **out, int64_t *out_len);
 
+/* Bytes [first, first + count) of the file a -n archive decodes to, written to out_host; *file_len (may be NULL) is the
+ * file's length: the header's where it carries one, otherwise the chunks are walked to the end.  Same header rules and
+ * refusals as mrz_runzip_buffer (MRZ_E_UNSUPPORTED, MRZ_E_CORRUPT); first < 0, count < 0 or a range beyond the file
+ * give MRZ_E_ARG, with *file_len set.  count == 0 takes out_host == NULL.
+ * Per chunk, stream 0's blocks are gathered as there and stream 1 only becomes a table of its blocks; a chunk's length
+ * comes from a host walk over its records.  Chunks outside the range do no device work and are not validated beyond
+ * that walk; a chunk inside it is validated whole and resolved by mrz_runzip_origins, and its bytes are gathered from
+ * the archive's blocks.  Behind a header that carries the size nothing past the range is looked at.
+ * The MD5 / per-chunk CRC is NOT checked: either needs every byte.  Use mrz_runzip_buffer for a verified decode. */
+int mrz_runzip_buffer_range(int device, const void *mrz, int64_t n, int64_t first, int64_t count, void *out_host,
+                            int64_t *file_len);
+
 #ifdef __cplusplus
 }
 #endif

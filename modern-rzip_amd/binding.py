@@ -51,6 +51,14 @@ class RsRange(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_int64), ("len", ctypes.c_int64)]
 
 
+class RangeInfo(ctypes.Structure):
+    """mrz_range_info (include/mrzgpu.h)."""
+    _fields_ = [("chunk_len", ctypes.c_int64), ("total_hops", ctypes.c_int64), ("max_hops", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Control(ctypes.Structure):
     """The rzip_control fields rzip_fd reads for `mrzip -n` (include/mrzgpu_host.h)."""
     _fields_ = [("rzip_compression_level", ctypes.c_int), ("compression_level", ctypes.c_int),
@@ -163,8 +171,14 @@ def load_library(path=None):
     if hasattr(lib, "mrz_runzip_chunk"):
         u32p = ctypes.POINTER(ctypes.c_uint32)
         lib.mrz_runzip_chunk.argtypes = [vp, vp, i64, vp, i64, ci, ci, vp, ci, i64, ctypes.POINTER(i64), u32p, u32p]
+    if hasattr(lib, "mrz_runzip_range"):
+        rip = ctypes.POINTER(RangeInfo)
+        lib.mrz_runzip_range.argtypes = [vp, vp, i64, vp, i64, ci, ci, i64, i64, vp, ci, rip]
+        lib.mrz_runzip_origins.argtypes = [vp, vp, i64, i64, ci, ci, i64, i64, vp, ci, rip]
     if hasattr(lib, "mrz_runzip_buffer"):
         lib.mrz_runzip_buffer.argtypes = [ci, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    if hasattr(lib, "mrz_runzip_buffer_range"):
+        lib.mrz_runzip_buffer_range.argtypes = [ci, vp, i64, i64, i64, vp, ctypes.POINTER(i64)]
     if hasattr(lib, "mrz_rzip_pipeline"):
         lib.mrz_rzip_pipeline.argtypes = [ctypes.POINTER(Control), vp, i64, BLOCK_FN, vp, ctypes.POINTER(Stats), vp]
     if hasattr(lib, "mrz_rzip_buffer"):
@@ -195,7 +209,9 @@ def _check(lib, rc, ctx=None):
         code = lib.mrz_last_hip_error(ctx, ctypes.byref(txt))
         if code:
             msg += f" (hip error {code}: {txt.value.decode() if txt.value else '?'})"
-    raise MrzError(f"libmrzgpu: {msg} [{rc}]")
+    err = MrzError(f"libmrzgpu: {msg} [{rc}]")
+    err.rc = rc
+    raise err
 
 
 def chunk_bytes(chunk_size, lib=None):
@@ -569,6 +585,57 @@ class RzipContext:
         _check(self.lib, rc, self.ctx)
         return None, got.value, cc.value, cs.value
 
+    def runzip_range(self, s0, s1, chunk_bytes_, first, count, out=None):
+        """mrz_runzip_range: bytes [first, first + count) of the chunk, without decoding the chunk and without a CRC.
+        Returns (bytes or None, dict(chunk_len, total_hops, max_hops)); with `out` = (device pointer, nbytes) or a cuda
+        tensor the bytes stay on the device.  Host streams: stream 1 is not uploaded, the bytes are gathered on the host.
+        count == 0 is the sizing call.  A refusal raises MrzError with .rc and, once the parse has succeeded, .info."""
+        if not hasattr(self.lib, "mrz_runzip_range"):
+            raise MrzError("this libmrzgpu has no mrz_runzip_range: rebuild it")
+        p0, n0, w0, k0 = _as_ptr(s0)
+        p1, n1, w1, k1 = _as_ptr(s1)
+        if w0 != w1:
+            raise MrzError("runzip_range: both streams must live in the same memory space")
+        info = RangeInfo(-1, 0, 0)
+        if out is None:
+            buf = ctypes.create_string_buffer(max(1, count))
+            po, wo = ctypes.cast(buf, ctypes.c_void_p), MEM_HOST
+        else:
+            po, no, wo, ko = _as_ptr(out)
+            if no < count:
+                raise MrzError("runzip_range: the output buffer is smaller than the range asked for")
+        rc = self.lib.mrz_runzip_range(self.ctx, p0, n0, p1, n1, w0, chunk_bytes_, first, count, po, wo, ctypes.byref(info))
+        self._check_range(rc, info)
+        return (buf.raw[:count] if out is None else None), info.as_dict()
+
+    def runzip_origins(self, s0, s1_len, chunk_bytes_, first, count, out=None):
+        """mrz_runzip_origins: the offset in stream 1 of every byte of [first, first + count); stream 1 itself is not
+        needed, only its length.  Returns (int64 numpy array or None, info dict); with `out` = a cuda int64 tensor or a
+        (device pointer, nbytes) pair the origins stay on the device."""
+        import numpy as np
+        if not hasattr(self.lib, "mrz_runzip_origins"):
+            raise MrzError("this libmrzgpu has no mrz_runzip_origins: rebuild it")
+        p0, n0, w0, k0 = _as_ptr(s0)
+        info = RangeInfo(-1, 0, 0)
+        if out is None:
+            arr = np.empty(max(1, count), dtype=np.int64)
+            po, wo = ctypes.c_void_p(arr.ctypes.data), MEM_HOST
+        else:
+            po, no, wo, ko = _as_ptr(out)
+            if no < count * 8:
+                raise MrzError("runzip_origins: the output buffer is smaller than the range asked for")
+        rc = self.lib.mrz_runzip_origins(self.ctx, p0, n0, s1_len, w0, chunk_bytes_, first, count, po, wo,
+                                         ctypes.byref(info))
+        self._check_range(rc, info)
+        return (arr[:count] if out is None else None), info.as_dict()
+
+    def _check_range(self, rc, info):
+        try:
+            _check(self.lib, rc, self.ctx)
+        except MrzError as e:
+            e.info = info.as_dict() if info.chunk_len >= 0 else None
+            raise
+
     # ---- BLAKE2b (common/blake2b.h:47-49) ----
     def blake2b(self, data, outlen=64, pieces=None):
         st = ctypes.c_void_p()
@@ -656,6 +723,26 @@ def runzip_buffer(mrz, device=0, lib=None):
         return ctypes.string_at(out, out_len.value)
     finally:
         lib.mrz_free(out)
+
+
+def runzip_buffer_range(mrz, first, count, device=0, lib=None):
+    """mrz_runzip_buffer_range: bytes [first, first + count) of the file a -n archive held in memory decodes to, without
+    decoding the rest and without the MD5 / CRC check.  Returns (bytes, file_len); a refusal raises MrzError with .rc and
+    .file_len (None where the archive was refused before its length was known)."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_runzip_buffer_range"):
+        raise MrzError("this libmrzgpu has no mrz_runzip_buffer_range: rebuild it")
+    ptr, n, where, keep = _as_ptr(mrz)
+    if where != MEM_HOST:
+        raise MrzError("runzip_buffer_range takes host memory")
+    buf = ctypes.create_string_buffer(max(1, count))
+    file_len = ctypes.c_int64(-1)
+    try:
+        _check(lib, lib.mrz_runzip_buffer_range(device, ptr, n, first, count, buf, ctypes.byref(file_len)))
+    except MrzError as e:
+        e.file_len = file_len.value if file_len.value >= 0 else None
+        raise
+    return buf.raw[:max(0, count)], file_len.value
 
 
 def rzip_pipeline(data, on_block, level=7, window=0, unlimited=False, ramsize=60 << 30, device=0, lib=None,

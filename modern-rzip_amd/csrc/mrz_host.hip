@@ -868,10 +868,10 @@ int64_t peek_le(const uint8_t *p, int nbytes) {
     return (int64_t)v;
 }
 
-// follows one stream's block chain and concatenates the payloads (fill_buffer, src/stream.c:1412-1571);
+// follows one stream's block chain (fill_buffer, src/stream.c:1412-1571) and hands every payload to block(p, len);
 // only CTYPE_NONE (3) blocks: the back-end codecs stay host code outside this library
-int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, std::vector<uint8_t> &dst,
-                  int64_t *end_max) {
+template <class F>
+int walk_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, F &&block, int64_t *end_max) {
     int64_t at = head_at;
     for (;;) {
         if (at + 1 + 3 * cb > n) return MRZ_E_CORRUPT;
@@ -882,7 +882,7 @@ int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t he
         if (c_len != u_len || c_len < 0) return MRZ_E_CORRUPT;
         const int64_t pay = at + 1 + 3 * cb;
         if (c_len > n - pay) return MRZ_E_CORRUPT;  // (compared without adding: a length field may be 2^63 - 1)
-        dst.insert(dst.end(), mrz + pay, mrz + pay + c_len);
+        block(mrz + pay, c_len);
         if (pay + c_len > *end_max) *end_max = pay + c_len;
         if (!next) return MRZ_OK;
         if (next < 0 || next > n - initial_pos || initial_pos + next <= at) return MRZ_E_CORRUPT;  // chains only run forward
@@ -890,23 +890,58 @@ int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t he
     }
 }
 
+// ... and concatenates the payloads
+int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, std::vector<uint8_t> &dst,
+                  int64_t *end_max) {
+    return walk_stream(mrz, n, initial_pos, head_at, cb,
+                       [&](const uint8_t *p, int64_t len) { dst.insert(dst.end(), p, p + len); }, end_max);
+}
+
+// bytes a chunk decodes to: the lengths of its records (host side: 3 or 3 + cb bytes each); false without a terminator
+bool records_out_len(const std::vector<uint8_t> &s0, int cb, int64_t *out_len) {
+    int64_t need = 0, i = 0;
+    const int64_t n0 = (int64_t)s0.size();
+    while (i + 3 <= n0) {
+        const int64_t len = s0[(size_t)i + 1] | (int64_t)s0[(size_t)i + 2] << 8;
+        if (s0[(size_t)i] == 0) {
+            if (len == 0) {
+                *out_len = need;
+                return true;
+            }
+            i += 3;
+        } else
+            i += 3 + cb;
+        need += len;
+    }
+    return false;
+}
+
+// the magic header (read_magic, src/mrzip.c:225-321): the size it carries (0: none) and the hash in use
+int read_archive_header(const uint8_t *mrz, int64_t n, int64_t *expected, int *hash_code) {
+    if (n < 20 || memcmp(mrz, "MRZI", 4)) return MRZ_E_CORRUPT;
+    if (mrz[15]) return MRZ_E_UNSUPPORTED;  // encrypted
+    *expected = peek_le(mrz + 6, 8);
+    *hash_code = mrz[14];
+    if (*hash_code != 0 && *hash_code != 1) return MRZ_E_UNSUPPORTED;  // MD5 (default) or CRC only
+    return MRZ_OK;
+}
+
 }  // namespace
 
 static int runzip_buffer_impl(int device, const void *mrz_v, int64_t n, void **out, int64_t *out_len) {
     if (!mrz_v || !out || !out_len) return MRZ_E_ARG;
     const uint8_t *mrz = (const uint8_t *)mrz_v;
-    if (n < 20 || memcmp(mrz, "MRZI", 4)) return MRZ_E_CORRUPT;  // read_magic, src/mrzip.c:225-321
-    if (mrz[15]) return MRZ_E_UNSUPPORTED;                        // encrypted
-    const int64_t expected = peek_le(mrz + 6, 8);
-    const int hash_code = mrz[14];
-    if (hash_code != 0 && hash_code != 1) return MRZ_E_UNSUPPORTED;  // MD5 (default) or CRC only
+    int64_t expected = 0;
+    int hash_code = 0;
+    int rc = read_archive_header(mrz, n, &expected, &hash_code);
+    if (rc) return rc;
     // an archive written to STDOUT in several chunks carries no size (src/mrzip.c:137-140): grow chunk by chunk
     const bool size_known = expected > 0;
     int64_t cap = size_known ? expected : 0;
     uint8_t *res = (uint8_t *)malloc((size_t)(cap > 0 ? cap : 1));
     if (!res) return MRZ_E_NOMEM;
     mrz_ctx *ctx = nullptr;
-    int rc = mrz_open(&ctx, device, 7, 0);
+    rc = mrz_open(&ctx, device, 7, 0);
     int64_t at = 20 + mrz[19], total = 0;
     std::vector<uint8_t> s0, s1;
     while (!rc) {  // runzip_chunk, src/runzip.c:226-330
@@ -929,23 +964,8 @@ static int runzip_buffer_impl(int device, const void *mrz_v, int64_t n, void **o
         if (!rc) rc = gather_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, s1, &end_max);
         if (rc) break;
         if (!size_known) {
-            // bytes this chunk decodes to: the lengths of its records (host side: 3 or 3 + cb bytes each)
-            int64_t need = 0, i = 0;
-            const int64_t n0 = (int64_t)s0.size();
-            bool ended = false;
-            while (i + 3 <= n0) {
-                const int64_t len = s0[(size_t)i + 1] | (int64_t)s0[(size_t)i + 2] << 8;
-                if (s0[(size_t)i] == 0) {
-                    if (len == 0) {
-                        ended = true;
-                        break;
-                    }
-                    i += 3;
-                } else
-                    i += 3 + cb;
-                need += len;
-            }
-            if (!ended) {
+            int64_t need = 0;
+            if (!records_out_len(s0, cb, &need)) {
                 rc = MRZ_E_CORRUPT;
                 break;
             }
@@ -995,6 +1015,141 @@ extern "C" int mrz_runzip_buffer(int device, const void *mrz_v, int64_t n, void 
     try {
         return runzip_buffer_impl(device, mrz_v, n, out, out_len);
     } catch (const std::bad_alloc &) {  // the header promises that the library never takes the host process down
+        return MRZ_E_NOMEM;
+    } catch (const std::length_error &) {
+        return MRZ_E_CORRUPT;
+    }
+}
+
+// ---- a byte range of the file a -n archive decodes to --------------------------------------------------------------
+namespace {
+
+struct StreamBlock {
+    const uint8_t *p;
+    int64_t start, len;  // stream offset of the payload's first byte
+};
+
+struct RangePart {  // a chunk that intersects the range
+    int cb;
+    std::vector<uint8_t> s0;
+    std::vector<StreamBlock> s1;  // the literal stream stays in the archive
+    int64_t s1_len;
+    int64_t lo, count;             // bytes [lo, lo + count) of the chunk ...
+    int64_t out_at;                // ... go to out_host + out_at
+};
+
+// n bytes of a stream from offset `at` through its block table
+void copy_from_blocks(const std::vector<StreamBlock> &blocks, int64_t at, int64_t n, uint8_t *dst) {
+    size_t lo = 0, hi = blocks.size();  // the last block that starts at or before `at`
+    while (hi - lo > 1) {
+        const size_t mid = (lo + hi) / 2;
+        if (blocks[mid].start <= at)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    while (n > 0) {
+        const StreamBlock &b = blocks[lo++];
+        const int64_t off = at - b.start;
+        const int64_t take = b.len - off < n ? b.len - off : n;
+        if (take > 0) memcpy(dst, b.p + off, (size_t)take);
+        dst += take;
+        at += take;
+        n -= take;
+    }
+}
+
+}  // namespace
+
+static int runzip_buffer_range_impl(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out_host,
+                                    int64_t *file_len) {
+    if (!mrz_v) return MRZ_E_ARG;
+    const uint8_t *mrz = (const uint8_t *)mrz_v;
+    int64_t expected = 0;
+    int hash_code = 0;
+    int rc = read_archive_header(mrz, n, &expected, &hash_code);
+    if (rc) return rc;
+    const bool size_known = expected > 0;
+    if (size_known) {
+        if (file_len) *file_len = expected;
+        if (first < 0 || count < 0 || first > expected || count > expected - first) return MRZ_E_ARG;
+        if (!count) return MRZ_OK;
+    }
+    // without a size the file's length is still owed to a caller whose range is wrong
+    const bool bad_range = first < 0 || count < 0 || count > INT64_MAX - first;
+    // the chunks: header, stream 0 gathered, stream 1 as a table, decoded length from the records
+    std::vector<RangePart> parts;
+    int64_t at = 20 + mrz[19], total = 0;
+    for (;;) {
+        if (at + 2 > n) return MRZ_E_CORRUPT;
+        const int cb = mrz[at], eof = mrz[at + 1];
+        if (cb < 1 || cb > 8 || at + 2 + cb > n) return MRZ_E_CORRUPT;
+        at += 2 + cb;
+        const int64_t initial_pos = at;
+        int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
+        RangePart part;
+        part.cb = cb;
+        part.s1_len = 0;
+        rc = gather_stream(mrz, n, initial_pos, initial_pos, cb, part.s0, &end_max);
+        if (!rc)
+            rc = walk_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb,
+                             [&](const uint8_t *p, int64_t len) {
+                                 part.s1.push_back(StreamBlock{ p, part.s1_len, len });
+                                 part.s1_len += len;
+                             },
+                             &end_max);
+        if (rc) return rc;
+        int64_t chunk_len = 0;
+        if (!records_out_len(part.s0, cb, &chunk_len)) return MRZ_E_CORRUPT;
+        if (!bad_range && count > 0 && total < first + count && total + chunk_len > first) {
+            const int64_t a = first > total ? first : total;
+            const int64_t b = first + count < total + chunk_len ? first + count : total + chunk_len;
+            part.lo = a - total;
+            part.count = b - a;
+            part.out_at = a - first;
+            parts.push_back(std::move(part));
+        }
+        total += chunk_len;
+        at = end_max;
+        if (size_known && total >= first + count) break;  // the range is covered
+        if (eof) break;
+    }
+    if (!size_known) {
+        if (file_len) *file_len = total;
+        if (bad_range || first > total || count > total - first) return MRZ_E_ARG;
+    } else if (total < first + count)
+        return MRZ_E_CORRUPT;  // fewer bytes than the header promised
+    if (!count) return MRZ_OK;
+    if (!out_host) return MRZ_E_ARG;
+
+    mrz_ctx *ctx = nullptr;
+    rc = mrz_open(&ctx, device, 7, 0);
+    std::vector<int64_t> origins;
+    for (size_t k = 0; !rc && k < parts.size(); k++) {
+        const RangePart &pt = parts[k];
+        origins.resize((size_t)pt.count);
+        mrz_range_info info;
+        rc = mrz_runzip_origins(ctx, pt.s0.data(), (int64_t)pt.s0.size(), pt.s1_len, MRZ_MEM_HOST, pt.cb, pt.lo, pt.count,
+                                origins.data(), MRZ_MEM_HOST, &info);
+        if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // the device's reading of the records differs from the host walk's
+        if (rc) break;
+        uint8_t *dst = (uint8_t *)out_host + pt.out_at;
+        for (int64_t i = 0; i < pt.count;) {  // runs of consecutive origins
+            int64_t j = i + 1;
+            while (j < pt.count && origins[(size_t)j] == origins[(size_t)j - 1] + 1) j++;
+            copy_from_blocks(pt.s1, origins[(size_t)i], j - i, dst + i);
+            i = j;
+        }
+    }
+    if (ctx) mrz_close(ctx);
+    return rc;
+}
+
+extern "C" int mrz_runzip_buffer_range(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count,
+                                       void *out_host, int64_t *file_len) {
+    try {
+        return runzip_buffer_range_impl(device, mrz_v, n, first, count, out_host, file_len);
+    } catch (const std::bad_alloc &) {
         return MRZ_E_NOMEM;
     } catch (const std::length_error &) {
         return MRZ_E_CORRUPT;

@@ -24,9 +24,15 @@
 //      tiles claimed before its own, i.e. by workgroups that are already running.
 // Then the CRC-32 kernel runs over the output.  Bound: HBM for literal-heavy input; on highly
 // repetitive input the copy chain (tile k needs tile k-1) is latency-bound.
+//
+// Range decode (mrz_runzip_range / mrz_runzip_origins) replaces pass 4 by mrz_uz_resolve_kernel: every byte of
+// [first, first + count) follows its match records backwards to the one stream-1 byte it comes from.  Independent per
+// byte: no output scratch, no ordering between workgroups, no literal read that is not delivered.  Its cost follows
+// the number of match records followed (hops), not the size of the chunk.
 #include <stdio.h>
 #include <string.h>
 
+#include <new>
 #include <vector>
 
 #include "mrz_ctx.h"
@@ -57,6 +63,8 @@ struct mrz_uz_hdr {
     int error;                // 1 = invalid record (distance 0 / beyond history, empty match), 2 = a wait gave up
     unsigned long long next_tile;   // decode pass: tile claim counter
     unsigned long long prefix_done; // decode pass: every tile below this index is complete
+    unsigned long long total_hops;  // range resolve: match records followed, summed over the bytes of the range
+    unsigned long long max_hops;    // ... and the most for one byte
 };
 
 struct mrz_uz_tile {          // per parse tile and entry offset
@@ -387,18 +395,131 @@ __global__ __launch_bounds__(MRZ_UZ_DEC_THREADS) void mrz_uz_decode_kernel(const
     }
 }
 
+// ---- range decode: the origin of single output bytes --------------------------------------------------------------
+
+// the record that holds output byte x: the last r in [0, hi] with rec[r].out_pos <= x (out_pos ascends strictly over
+// the records in front of the terminator, and rec[0].out_pos == 0)
+__device__ __forceinline__ int64_t mrz_uz_find(const mrz_urec *__restrict__ rec, int64_t x, int64_t hi) {
+    int64_t lo = 0;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (rec[mid].out_pos <= x)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// a value that is the same in every lane of the wave, said so to the compiler: searches on it use scalar loads.  (The
+// emulator has nothing to gain from it, and a collective per pass there costs more than the pass.)
+__device__ __forceinline__ int64_t mrz_uz_uniform64(int64_t v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return mrz_uni64(v);
+#else
+    return v;
+#endif
+}
+
+// Every output byte has exactly one origin in stream 1: a literal record gives it directly, a match record sends
+// position x to out_pos - dist + (x - out_pos) % min(len, dist) (unzip_match's "first min(len, dist) history bytes
+// repeat", src/runzip.c:182-199), which lies in front of the record -- one hop; x falls strictly, so the walk ends.
+// A lane owns one byte per pass and a wave 64 consecutive ones, so the stores coalesce.  The wave searches once for
+// the record of its first byte, with wave-uniform operands; where the 64 positions fall into that record -- the common
+// case -- nobody searches again, and a lane whose byte lies elsewhere searches for itself.  That test is the divergent
+// branch itself: the wave skips it when no lane takes it, and no collective is needed to say so.  From then on every
+// lane walks alone (lanes that stay in one record make the same loads in step); the record a hop leaves bounds the
+// next search from above.  No LDS, nothing shared between workgroups, no wait on memory.
+// ORIGINS: dst[i] = stream-1 offset of output byte first + i (int64); otherwise dst[i] = s1[that offset].
+// nrec counts the records in front of the terminator, which is rec[nrec].  A walk of more than nrec hops cannot
+// happen on validated records; it ends with hdr->error = 2 instead of running on.
+template <bool ORIGINS>
+__global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_resolve_kernel(const mrz_urec *__restrict__ rec, int64_t nrec,
+                                                                        const uint8_t *__restrict__ s1, int64_t first,
+                                                                        int64_t count, void *__restrict__ dst,
+                                                                        mrz_uz_hdr *__restrict__ hdr) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t stride = (int64_t)gridDim.x * MRZ_UZ_THREADS;
+    int64_t sum_hops = 0, top_hops = 0;
+    // `base` is the wave's first byte of the pass (the same in all its lanes)
+    const int64_t base0 = mrz_uz_uniform64((int64_t)blockIdx.x * MRZ_UZ_THREADS + (threadIdx.x - lane));
+    if (base0 >= count) return;  // the whole wave: nothing to resolve, nothing to report
+    for (int64_t base = base0; base < count; base += stride) {
+        int64_t r = mrz_uz_find(rec, first + base, nrec - 1);  // once per wave
+        int64_t o = rec[r].out_pos, o_end = rec[r + 1].out_pos;
+        const int64_t i = base + lane;
+        int64_t hops = 0, origin = 0;
+        if (i < count) {
+            int64_t x = first + i, hi = nrec - 1;
+            if (x >= o_end) {  // (x >= o holds: x >= first + base) not the wave's record
+                r = mrz_uz_find(rec, x, hi);
+                o = rec[r].out_pos;
+                o_end = rec[r + 1].out_pos;
+            }
+            while (true) {
+                const unsigned long long src = rec[r].src;
+                if (!(src & MRZ_UZ_MATCH)) {
+                    origin = (int64_t)src + (x - o);
+                    break;
+                }
+                if (hops >= nrec) {
+                    hdr->error = 2;
+                    break;
+                }
+                const int64_t dist = (int64_t)(src & ~MRZ_UZ_MATCH), len = o_end - o;
+                const int64_t span = len < dist ? len : dist;
+                const int64_t k = x - o;
+                x = o - dist + (k < span ? k : k % span);
+                hops++;
+                hi = r;
+                r = mrz_uz_find(rec, x, hi);
+                o = rec[r].out_pos;
+                o_end = rec[r + 1].out_pos;
+            }
+        }
+        if (i < count) {
+            if (ORIGINS)
+                ((int64_t *)dst)[i] = origin;
+            else
+                ((uint8_t *)dst)[i] = s1[origin];
+        }
+        sum_hops += hops;
+        top_hops = hops > top_hops ? hops : top_hops;
+    }
+    // statistics: reduce over the wave, then one atomic each per wave
+    for (int d = 32; d; d >>= 1) {
+        sum_hops += mrz_shfl_xor64(sum_hops, d);
+        const int64_t t = mrz_shfl_xor64(top_hops, d);
+        top_hops = t > top_hops ? t : top_hops;
+    }
+    if (lane == 0 && sum_hops) {
+        atomicAdd(&hdr->total_hops, (unsigned long long)sum_hops);
+        unsigned long long seen = __hip_atomic_load(&hdr->max_hops, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        while ((unsigned long long)top_hops > seen) {
+            const unsigned long long was = atomicCAS(&hdr->max_hops, seen, (unsigned long long)top_hops);
+            if (was == seen) break;
+            seen = was;
+        }
+    }
+}
+
 static int uz_grow(mrz_ctx *ctx, int64_t want) {
     return mrz_grow(ctx, (uint8_t **)&ctx->rz_scratch, &ctx->rz_scratch_cap, want);
 }
 
-extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
-                                int chunk_bytes, void *out, int out_where, int64_t out_cap, int64_t *out_len,
-                                uint32_t *crc_calc, uint32_t *crc_stored) {
-    if (!ctx || !s0 || s0_len < 7 || s1_len < 0 || (s1_len > 0 && !s1) || chunk_bytes < 1 || chunk_bytes > 8 || !out_len)
-        return MRZ_E_ARG;
-    if ((where != MRZ_MEM_HOST && where != MRZ_MEM_DEVICE) || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE))
-        return MRZ_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// what the three parse launches leave behind
+struct uz_parsed {
+    mrz_uz_hdr h;           // as of the end of the parse
+    mrz_uz_hdr *d_hdr;
+    mrz_urec *d_rec;        // h.nrec records and the terminator's
+    const uint8_t *d_s0;
+    uint8_t *d_extra;       // `extra` bytes of scratch behind everything else (the staged stream 1 of a host call)
+};
+
+// Uploads stream 0 when it is host memory -- and `up_len` bytes of `up` to d_extra along with it --, runs the two parse
+// passes and the scan, and waits for the header.  The verdict on the stream (p->h) is the caller's to read.
+static int uz_parse(mrz_ctx *ctx, const void *s0, int64_t s0_len, int where, int chunk_bytes, int64_t extra,
+                    const void *up, int64_t up_len, uz_parsed *p) {
     hipStream_t s = ctx->stream;
     const int64_t ntiles = (s0_len + MRZ_UZ_PT - 1) / MRZ_UZ_PT;
     const int64_t max_rec = s0_len / 3 + 2;
@@ -410,8 +531,8 @@ extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, co
     const int64_t o_bases = o_tiles + al(ntiles * (int64_t)sizeof(mrz_uz_tile));
     const int64_t o_rec = o_bases + al(ntiles * (int64_t)sizeof(mrz_uz_base));
     const int64_t o_s0 = o_rec + al(max_rec * (int64_t)sizeof(mrz_urec));
-    const int64_t o_s1 = o_s0 + (where == MRZ_MEM_HOST ? al(s0_len + 64) : 0);
-    const int64_t o_end = o_s1 + (where == MRZ_MEM_HOST ? al(s1_len + 64) : 0);
+    const int64_t o_extra = o_s0 + (where == MRZ_MEM_HOST ? al(s0_len + 64) : 0);
+    const int64_t o_end = o_extra + al(extra);
     int rc = uz_grow(ctx, o_end);
     if (rc) return rc;
     uint8_t *base = (uint8_t *)ctx->rz_scratch;
@@ -419,12 +540,11 @@ extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, co
     mrz_uz_tile *d_tiles = (mrz_uz_tile *)(base + o_tiles);
     mrz_uz_base *d_bases = (mrz_uz_base *)(base + o_bases);
     mrz_urec *d_rec = (mrz_urec *)(base + o_rec);
-    const uint8_t *d_s0 = (const uint8_t *)s0, *d_s1 = (const uint8_t *)s1;
+    const uint8_t *d_s0 = (const uint8_t *)s0;
     if (where == MRZ_MEM_HOST) {
         HIPCHK(ctx, hipMemcpyAsync(base + o_s0, s0, (size_t)s0_len, hipMemcpyHostToDevice, s));
-        if (s1_len) HIPCHK(ctx, hipMemcpyAsync(base + o_s1, s1, (size_t)s1_len, hipMemcpyHostToDevice, s));
+        if (up_len) HIPCHK(ctx, hipMemcpyAsync(base + o_extra, up, (size_t)up_len, hipMemcpyHostToDevice, s));
         d_s0 = base + o_s0;
-        d_s1 = base + o_s1;
     }
     HIPCHK(ctx, hipMemsetAsync(d_hdr, 0, sizeof(mrz_uz_hdr), s));
     const int ph = 3 + chunk_bytes;
@@ -438,9 +558,31 @@ extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, co
                            dim3(MRZ_UZ_THREADS), 0, s, d_s0, s0_len, chunk_bytes, ntiles, d_bases, d_rec, d_hdr);
         HIPCHK(ctx, hipGetLastError());
     }
-    mrz_uz_hdr h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(&p->h, d_hdr, sizeof(p->h), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
+    p->d_hdr = d_hdr;
+    p->d_rec = d_rec;
+    p->d_s0 = d_s0;
+    p->d_extra = base + o_extra;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
+                                int chunk_bytes, void *out, int out_where, int64_t out_cap, int64_t *out_len,
+                                uint32_t *crc_calc, uint32_t *crc_stored) {
+    if (!ctx || !s0 || s0_len < 7 || s1_len < 0 || (s1_len > 0 && !s1) || chunk_bytes < 1 || chunk_bytes > 8 || !out_len)
+        return MRZ_E_ARG;
+    if ((where != MRZ_MEM_HOST && where != MRZ_MEM_DEVICE) || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE))
+        return MRZ_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    uz_parsed ps;
+    int rc = uz_parse(ctx, s0, s0_len, where, chunk_bytes, where == MRZ_MEM_HOST ? s1_len + 64 : 0, s1, s1_len, &ps);
+    if (rc) return rc;
+    mrz_uz_hdr h = ps.h;
+    mrz_uz_hdr *d_hdr = ps.d_hdr;
+    mrz_urec *d_rec = ps.d_rec;
+    const uint8_t *d_s0 = ps.d_s0, *d_s1 = where == MRZ_MEM_HOST ? ps.d_extra : (const uint8_t *)s1;
     if (h.final_state != MRZ_UZ_END || h.error || h.lit_total > s1_len) return MRZ_E_CORRUPT;
     *out_len = h.out_total;
     if (h.out_total > out_cap || (h.out_total > 0 && !out)) return MRZ_E_ARG;
@@ -487,4 +629,106 @@ extern "C" int mrz_runzip_chunk(mrz_ctx *ctx, const void *s0, int64_t s0_len, co
     if (crc_stored)
         *crc_stored = (uint32_t)stored[0] << 24 | (uint32_t)stored[1] << 16 | (uint32_t)stored[2] << 8 | stored[3];
     return MRZ_OK;
+}
+
+// bytes or origins of [first, first + count): see include/mrzgpu.h
+static int uz_range(mrz_ctx *ctx, bool want_origins, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len,
+                    int where, int chunk_bytes, int64_t first, int64_t count, void *out, int out_where,
+                    mrz_range_info *info) {
+    if (!ctx || !s0 || s0_len < 7 || s1_len < 0 || chunk_bytes < 1 || chunk_bytes > 8) return MRZ_E_ARG;
+    if (!want_origins && s1_len > 0 && !s1) return MRZ_E_ARG;
+    if ((where != MRZ_MEM_HOST && where != MRZ_MEM_DEVICE) || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE))
+        return MRZ_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    uz_parsed ps;
+    int rc = uz_parse(ctx, s0, s0_len, where, chunk_bytes, 0, nullptr, 0, &ps);
+    if (rc) return rc;
+    const mrz_uz_hdr &h = ps.h;
+    if (h.final_state != MRZ_UZ_END || h.error || h.lit_total > s1_len) return MRZ_E_CORRUPT;
+    if (info) {
+        info->chunk_len = h.out_total;
+        info->total_hops = info->max_hops = 0;
+    }
+    if (first < 0 || count < 0 || first > h.out_total || count > h.out_total - first) return MRZ_E_ARG;
+    if (!count) return MRZ_OK;
+    if (!out) return MRZ_E_ARG;
+
+    // a host-resident stream 1 stays where it is: its origins are resolved here and the bytes gathered on the host
+    const bool origins = want_origins || where == MRZ_MEM_HOST;
+    const bool direct = out_where == MRZ_MEM_DEVICE && origins == want_origins;  // the kernel writes `out` itself
+    if (direct && want_origins && ((uintptr_t)out & 7)) return MRZ_E_ARG;
+    const int64_t item = origins ? 8 : 1;
+    void *d_dst = out;
+    if (!direct) {
+        rc = mrz_grow(ctx, &ctx->d_rz_out, &ctx->rz_out_cap, count * item);
+        if (rc) return rc;
+        d_dst = ctx->d_rz_out;
+    }
+    int cus = 0;
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    int64_t grid = (int64_t)(cus > 0 ? cus : 64) * 8;  // 32 waves per CU in flight: the walk is a chain of dependent loads
+    const int64_t blocks = (count + MRZ_UZ_THREADS - 1) / MRZ_UZ_THREADS;
+    if (grid > blocks) grid = blocks;
+    if (origins)
+        hipLaunchKernelGGL(mrz_uz_resolve_kernel<true>, dim3((unsigned)grid), dim3(MRZ_UZ_THREADS), 0, s, ps.d_rec, h.nrec,
+                           (const uint8_t *)nullptr, first, count, d_dst, ps.d_hdr);
+    else
+        hipLaunchKernelGGL(mrz_uz_resolve_kernel<false>, dim3((unsigned)grid), dim3(MRZ_UZ_THREADS), 0, s, ps.d_rec, h.nrec,
+                           (const uint8_t *)s1, first, count, d_dst, ps.d_hdr);
+    HIPCHK(ctx, hipGetLastError());
+    mrz_uz_hdr after;
+    HIPCHK(ctx, hipMemcpyAsync(&after, ps.d_hdr, sizeof(after), hipMemcpyDeviceToHost, s));
+    std::vector<int64_t> h_org;
+    if (!direct && origins && !want_origins) {  // bytes asked for, stream 1 on the host
+        h_org.resize((size_t)count);
+        HIPCHK(ctx, hipMemcpyAsync(h_org.data(), d_dst, (size_t)count * 8, hipMemcpyDeviceToHost, s));
+    } else if (!direct)
+        HIPCHK(ctx, hipMemcpyAsync(out, d_dst, (size_t)(count * item), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (after.error) return after.error == 2 ? MRZ_E_STATE : MRZ_E_CORRUPT;
+    if (info) {
+        info->total_hops = (int64_t)after.total_hops;
+        info->max_hops = (int64_t)after.max_hops;
+    }
+    if (!h_org.empty()) {
+        // consecutive bytes mostly have consecutive origins: copy runs
+        std::vector<uint8_t> staged;
+        uint8_t *dst = (uint8_t *)out;
+        if (out_where == MRZ_MEM_DEVICE) {
+            staged.resize((size_t)count);
+            dst = staged.data();
+        }
+        const uint8_t *lit = (const uint8_t *)s1;
+        for (int64_t i = 0; i < count;) {
+            int64_t j = i + 1;
+            while (j < count && h_org[(size_t)j] == h_org[(size_t)j - 1] + 1) j++;
+            memcpy(dst + i, lit + h_org[(size_t)i], (size_t)(j - i));
+            i = j;
+        }
+        if (out_where == MRZ_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpyAsync(out, dst, (size_t)count, hipMemcpyHostToDevice, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+    }
+    return MRZ_OK;
+}
+
+extern "C" int mrz_runzip_range(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
+                                int chunk_bytes, int64_t first, int64_t count, void *out, int out_where,
+                                mrz_range_info *info) {
+    try {
+        return uz_range(ctx, false, s0, s0_len, s1, s1_len, where, chunk_bytes, first, count, out, out_where, info);
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+}
+
+extern "C" int mrz_runzip_origins(mrz_ctx *ctx, const void *s0, int64_t s0_len, int64_t s1_len, int where, int chunk_bytes,
+                                  int64_t first, int64_t count, int64_t *origins, int out_where, mrz_range_info *info) {
+    try {
+        return uz_range(ctx, true, s0, s0_len, nullptr, s1_len, where, chunk_bytes, first, count, origins, out_where, info);
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
 }
