@@ -181,6 +181,22 @@ int mrz_set_cand_provider(mrz_ctx *ctx, mrz_cand_provider_fn fn, void *user);
  * default 8 Mi = 128 MiB) */
 int mrz_set_segment_positions(mrz_ctx *ctx, int64_t positions);
 int mrz_set_candidate_capacity(mrz_ctx *ctx, int64_t entries);
+/* TEST KNOB (as the two above): when mrz_rzip_chunk learns what its queued segment launches did.  It keeps up to 4
+ * launches in flight and, by default, retires whichever have completed (hipEventQuery) before it prepares the next --
+ * so the matcher state it plans with (mask, position, engine hints) lags by 0..3 launches, as the host's timing has
+ * it.  With a schedule set the poll is deterministic instead: once `hold` launches (1..4) are in flight it waits for
+ * the oldest and retires it (all = 0) or every launch in flight (all = 1); with fewer in flight it retires none.  The
+ * waits the loop is forced into (full queue, everything queued, the room rule) stay as they are.  (1, 1) is a host that
+ * always knows; (4, 0) plans every launch on news three launches old; (h, 1) retires in bursts.  The output is the same
+ * bytes under every schedule.  hold <= 0: back to the default; hold > 4 or all not 0 / 1: MRZ_E_ARG.  From the next chunk
+ * on.  The MRZ_RETIRE_SCHEDULE environment variable ("<hold>:one" or "<hold>:all"), read by mrz_open, sets a ctx's
+ * initial value; a malformed value means the default. */
+int mrz_set_retire_schedule(mrz_ctx *ctx, int hold, int all);
+/* What the host loop of the last chunk did (under any schedule): out[0] launches retired, out[1] the most launches
+ * retired by one poll, out[2] the most launches in flight when a launch was prepared (how stale its plan was at most),
+ * out[3] launches that sequenced nothing (their snapshot shows the position, match count and insert count of the one
+ * before, and not the end of the chunk: launches planned on news the device had overtaken). */
+int mrz_schedule_info(const mrz_ctx *ctx, int64_t out[4]);
 /* host -> device / device -> device copy on the ctx stream (what a provider without a HIP runtime of its own fills the
  * buffers with); returns when the source may be reused */
 int mrz_copy_to_device(mrz_ctx *ctx, void *dst_device, const void *src_host, int64_t n);

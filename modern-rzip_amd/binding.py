@@ -127,6 +127,10 @@ def load_library(path=None):
         lib.mrz_set_candidate_capacity.argtypes = [vp, i64]
     if hasattr(lib, "mrz_set_event_capacity"):
         lib.mrz_set_event_capacity.argtypes = [vp, i64]
+    if hasattr(lib, "mrz_set_retire_schedule"):
+        lib.mrz_set_retire_schedule.argtypes = [vp, ci, ci]
+        lib.mrz_schedule_info.argtypes = [vp, ctypes.POINTER(i64 * 4)]
+    if hasattr(lib, "mrz_set_xcd"):
         lib.mrz_set_xcd.argtypes = [vp, ci]
         lib.mrz_copy_to_device.argtypes = [vp, vp, vp, i64]
         lib.mrz_copy_device.argtypes = [vp, vp, vp, i64]
@@ -321,6 +325,19 @@ class RzipContext:
         """mrz_set_event_capacity: entries of the device match list from the next chunk on (1024 .. 2^31; <= 0: the
         default).  A chunk that can emit more matches is encoded in pieces (timings().n_event_flushes)."""
         _check(self.lib, self.lib.mrz_set_event_capacity(self.ctx, entries), self.ctx)
+
+    def set_retire_schedule(self, hold, all=False):
+        """mrz_set_retire_schedule (a test knob): from the next chunk on the host retires its queued segment launches
+        only once `hold` (1..4) are in flight -- the oldest one, or all of them with all=True.  hold <= 0: back to polling
+        the launches' events."""
+        _check(self.lib, self.lib.mrz_set_retire_schedule(self.ctx, hold, 1 if all else 0), self.ctx)
+
+    def schedule_info(self):
+        """mrz_schedule_info of the last chunk: (launches retired, most launches retired by one poll, most launches in
+        flight when a launch was prepared, launches that sequenced nothing)."""
+        out = (ctypes.c_int64 * 4)()
+        _check(self.lib, self.lib.mrz_schedule_info(self.ctx, ctypes.byref(out)), self.ctx)
+        return tuple(out)
 
     def set_xcd(self, xcd):
         _check(self.lib, self.lib.mrz_set_xcd(self.ctx, xcd), self.ctx)

@@ -169,6 +169,15 @@ extern "C" int mrz_open(mrz_ctx **out, int device, int level, int64_t max_chunk)
                 fprintf(stderr, "libmrzgpu: MRZ_EVENT_CAPACITY=%s ignored (%lld .. %lld entries)\n", c, MRZ_EVENT_MIN,
                         MRZ_EVENT_MAX);
         }
+        if (const char *r = getenv("MRZ_RETIRE_SCHEDULE")) {  // (as mrz_set_retire_schedule; malformed: the default)
+            const int hold = r[0] - '0';
+            const bool one = r[0] && !strcmp(r + 1, ":one"), all = r[0] && !strcmp(r + 1, ":all");
+            if (hold >= 1 && hold <= MRZ_SEG_AHEAD && (one || all))
+                ctx->retire_hold = hold, ctx->retire_all = all ? 1 : 0;
+            else
+                fprintf(stderr, "libmrzgpu: MRZ_RETIRE_SCHEDULE=%s ignored (<1..%d>:one or <1..%d>:all)\n", r, MRZ_SEG_AHEAD,
+                        MRZ_SEG_AHEAD);
+        }
     }
     ctx->farm_default = mrz_sequencer_default_helpers(device);
     ctx->device = device;
@@ -325,6 +334,19 @@ extern "C" int mrz_set_candidate_capacity(mrz_ctx *ctx, int64_t entries) {
 extern "C" int mrz_set_event_capacity(mrz_ctx *ctx, int64_t entries) {
     if (!ctx || (entries > 0 && entries < MRZ_EVENT_MIN) || entries > MRZ_EVENT_MAX) return MRZ_E_ARG;
     ctx->event_cap_set = entries > 0 ? entries : 0;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_set_retire_schedule(mrz_ctx *ctx, int hold, int all) {
+    if (!ctx || hold > MRZ_SEG_AHEAD || (hold > 0 && all != 0 && all != 1)) return MRZ_E_ARG;
+    ctx->retire_hold = hold > 0 ? hold : 0;
+    ctx->retire_all = hold > 0 ? all : 0;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_schedule_info(const mrz_ctx *ctx, int64_t out[4]) {
+    if (!ctx || !out) return MRZ_E_ARG;
+    memcpy(out, ctx->sched_info, sizeof(ctx->sched_info));
     return MRZ_OK;
 }
 
@@ -599,21 +621,32 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     int64_t hint_pos = 0, hint_matched = 0;
     int64_t known_events = 0, known_last = 0;  // matches emitted by the last retired launch, and where the last one ended
     bool finished = end <= 0;
+    // the retirement schedule (mrz_set_retire_schedule: a test knob; 0 = poll the events) and what mrz_schedule_info reports
+    const int hold = ctx->retire_hold, hold_all = ctx->retire_all;
+    int64_t max_burst = 0, max_lag = 0, n_idle = 0, prev_p = 0, prev_events = 0, prev_inserts = 0;
+    int64_t resume_seen = 0;  // (window sharding) launches before this one were prepared before the last resume point was known
+    memset(ctx->sched_info, 0, sizeof(ctx->sched_info));
     // a launch whose event has completed: its snapshot is final
     auto retire = [&]() {
         const mrz_seq_state *sn = &ctx->h_ring[retired % MRZ_SEG_AHEAD];
-        retired++;
+        const int64_t idx = retired++;
+        if (!sn->finished && sn->p == prev_p && sn->n_events == prev_events && sn->inserts == prev_inserts) n_idle++;
+        prev_p = sn->p, prev_events = sn->n_events, prev_inserts = sn->inserts;
         known_p = sn->p;
         known_mask = sn->min_mask;
         known_events = sn->n_events;
         known_last = sn->last_match;
         if (!ctx->cand_fn)
             known_next = sn->scan_next;
-        else if (sn->seg_end > sn->seg_start && sn->scan_next < sn->seg_end)
+        else if (sn->seg_end > sn->seg_start && sn->scan_next < sn->seg_end && idx >= resume_seen) {
             // (window sharding, where the host drives the geometry: the wide engine has ended this launch where the mask
             // reached the deep engine's regime and taken scan_next back to its position -- the next stretch is asked for
-            // from there)
+            // from there.  The launches in flight right now were prepared for stretches beyond the one that was cut
+            // short: they sequence nothing and report the same resume point, which by then is old news -- a stretch from
+            // it has been queued, and known_next is where that one ends.)
             known_next = sn->scan_next;
+            resume_seen = launched;
+        }
         hint_pos = sn->hint_positions;
         hint_matched = sn->hint_matched;
         if (ctx->progress_fn) {
@@ -671,7 +704,19 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     if (pass_cap < MRZ_TILE) pass_cap = MRZ_TILE;
     while (!finished && herr == hipSuccess && !rc) {
         // whatever has completed meanwhile (the engine choice and the span below want the matcher's latest news)
-        while (retired < launched && !finished && !rc && hipEventQuery(seg_ev[retired % MRZ_SEG_AHEAD]) == hipSuccess) retire();
+        const int64_t retired0 = retired;
+        if (!hold)
+            while (retired < launched && !finished && !rc && hipEventQuery(seg_ev[retired % MRZ_SEG_AHEAD]) == hipSuccess) retire();
+        else if (launched - retired >= hold) {
+            // (the schedule of mrz_set_retire_schedule: the oldest launch, or all of them, once `hold` are in flight)
+            const int64_t upto = hold_all ? launched : retired + 1;
+            while (retired < upto && !finished && !rc && herr == hipSuccess) {
+                STEP(hipEventSynchronize(seg_ev[retired % MRZ_SEG_AHEAD]));
+                if (herr == hipSuccess) retire();
+            }
+            if (herr != hipSuccess) break;
+        }
+        if (retired - retired0 > max_burst) max_burst = retired - retired0;
         if (finished || rc) break;
         // where the queued passes will have got to if none of them is cut short
         int64_t est_next = known_next;
@@ -745,6 +790,7 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
                 max_tiles = span / MRZ_TILE;
             }
         }
+        if (launched - retired > max_lag) max_lag = launched - retired;  // (this launch is planned on news that old)
         PROF_BEGIN(0);
         if (ctx->cand_fn) {
             // window sharding: the stretch's owner scans it (with the mask this rank has last heard of); the host drives
@@ -851,6 +897,10 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     ctx->timings.n_narrow = (int32_t)n_narrow;
     ctx->timings.n_deep = (int32_t)n_deep;
     ctx->timings.n_event_flushes = (int32_t)n_flushes;
+    ctx->sched_info[0] = retired;
+    ctx->sched_info[1] = max_burst;
+    ctx->sched_info[2] = max_lag;
+    ctx->sched_info[3] = n_idle;
     if (ctx->profiling) {
         hipStreamSynchronize(s);
         for (int i = 0; i < nev; i++) {

@@ -95,6 +95,8 @@ struct mrz_ctx {
     void *progress_user;
     int64_t events_final;     // matches of the chunk in flight that are final (mrz_fetch_events bound)
     int64_t seg_positions;    // positions per front-end pass at most (MRZ_SEG_POSITIONS unless a test shrinks it)
+    int retire_hold, retire_all;   // mrz_set_retire_schedule / MRZ_RETIRE_SCHEDULE (test knob); hold 0 = poll the events
+    int64_t sched_info[4];         // mrz_schedule_info of the last chunk
     mrz_cand_provider_fn cand_fn;  // window sharding: the rank that owns a stretch of the window scans it
     void *cand_user;
 };

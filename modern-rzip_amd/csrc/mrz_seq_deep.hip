@@ -826,6 +826,11 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
     int64_t ci;
     {
         int64_t pos = L.p + 1;
+        // (The clamp would step over a gap between p + 1 and seg_start without a word.  By reading, no deep launch sees
+        // one: the only gap is the one a wide launch leaves when it ends early at this engine's mask under a candidate
+        // provider, and the host chooses this engine only on a retired snapshot that carries that mask -- the one that
+        // reports the resume point, or a later one -- so the stretch it lays out begins at the resume point or at the
+        // tile of p + 1.  With the engine pinned to deep no launch ends early.  No test reaches a gap here.)
         if (pos < K.seg_start) pos = K.seg_start;
         ci = mrz_cand_lower_bound(K, pos, lane);
     }

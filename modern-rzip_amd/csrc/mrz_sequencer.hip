@@ -121,11 +121,14 @@ __global__ __launch_bounds__(MRZ_SEQ_THREADS) void mrz_sequencer_kernel(mrz_seq_
 
     if (st->finished || st->error) return;
     // the mask has reached the deep engine's regime (a launch queued before the host knew): nothing is sequenced here,
-    // the front end scans this stretch again (under the tighter mask) for the deep engine's launch
+    // the front end scans this stretch again (under the tighter mask) for the deep engine's launch.  scan_next goes back
+    // to the matcher's tile, NOT to this launch's seg_start: under a candidate provider the host lays the stretches out,
+    // and this one may begin beyond the point where the launch before ended early -- nothing in between has been
+    // sequenced.  (With the front end's own geometry seg_start is that tile.)
     if (a.deep_bits > 0 && __popcll((unsigned long long)st->min_mask) >= a.deep_bits) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             const int64_t pt = ((st->p + 1) >> MRZ_TILE_SHIFT) << MRZ_TILE_SHIFT;
-            if (st->seg_end > st->seg_start && pt < st->scan_next) st->scan_next = pt > st->seg_start ? pt : st->seg_start;
+            if (st->seg_end > st->seg_start && pt < st->scan_next) st->scan_next = pt;
         }
         return;
     }

@@ -1,5 +1,6 @@
 """Randomised parity sweep on the GPU: mrz_rzip_chunk (+ mrz_runzip_chunk) against the oracle on random shapes,
-sizes, levels and victim_round values.  usage: [FUZZ_BIG=1] python tools/fuzz_parity.py [seconds] [seed]"""
+sizes, levels and victim_round values.  usage: [FUZZ_BIG=1] python tools/fuzz_parity.py [seconds] [seed]
+MRZ_RETIRE_SCHEDULE=<1..4>:one|all in the environment applies to every ctx of the sweep."""
 import os, random, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import modern_rzip_amd as m
