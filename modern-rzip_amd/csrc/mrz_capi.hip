@@ -6,7 +6,9 @@
 #include <string.h>
 
 #include "../../include/mrzgpu.h"
+#include "mrz_chunk_plan.h"
 #include "mrz_ctx.h"
+#include "mrz_seq_stats.h"
 
 
 
@@ -492,18 +494,335 @@ extern "C" int mrz_crc32(mrz_ctx *ctx, const void *buf, int64_t n, int where, ui
     return MRZ_OK;
 }
 
-struct mrz_evpair {
-    hipEvent_t a, b;
-    int kind;  // 0 front end, 1 sequencer, 2 encode, 3 crc
+// HIP event pairs around the stages of a chunk (mrz_set_profiling).  Owns its events: whatever path the call leaves by,
+// they are destroyed.
+struct mrz_prof_spans {
+    struct pair {
+        hipEvent_t a, b;
+        int kind;  // 0 front end, 1 sequencer, 2 encode, 3 crc
+    };
+    const bool on;
+    const hipStream_t s;
+    pair *v = nullptr;
+    int n = 0, cap = 0;
+    bool open = false;  // v[n] has been begun
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+
+    mrz_prof_spans(bool enabled, hipStream_t stream) : on(enabled), s(stream) {
+        if (!on) return;
+        hipEventCreate(&ev_begin);
+        hipEventCreate(&ev_end);
+        hipEventRecord(ev_begin, s);
+    }
+    mrz_prof_spans(const mrz_prof_spans &) = delete;
+    ~mrz_prof_spans() {
+        for (int i = 0; i < n + (open ? 1 : 0); i++) {
+            hipEventDestroy(v[i].a);
+            hipEventDestroy(v[i].b);
+        }
+        free(v);
+        if (ev_begin) hipEventDestroy(ev_begin);
+        if (ev_end) hipEventDestroy(ev_end);
+    }
+    void begin(int kind) {
+        if (!on) return;
+        if (n == cap) {
+            const int ncap = cap ? cap * 2 : 64;
+            pair *nv = (pair *)realloc(v, (size_t)ncap * sizeof(pair));
+            if (nv) v = nv, cap = ncap;
+        }
+        if (n < cap) {
+            v[n].kind = kind;
+            hipEventCreate(&v[n].a);
+            hipEventCreate(&v[n].b);
+            hipEventRecord(v[n].a, s);
+            open = true;
+        }
+    }
+    void end() {
+        if (!open) return;
+        hipEventRecord(v[n].b, s);
+        open = false;
+        n++;
+    }
+    void end_total() {
+        if (on) hipEventRecord(ev_end, s);
+    }
+    void collect(mrz_timings *t) {
+        if (!on) return;
+        hipStreamSynchronize(s);
+        for (int i = 0; i < n; i++) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, v[i].a, v[i].b) != hipSuccess) continue;
+            if (v[i].kind == 0) t->tagscan_ms += ms;
+            if (v[i].kind == 1) t->sequencer_ms += ms;
+            if (v[i].kind == 2) t->encode_ms += ms;
+            if (v[i].kind == 3) t->crc_ms += ms;
+        }
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev_begin, ev_end) == hipSuccess) t->total_ms = ms;
+    }
 };
 
-// positions a front-end pass should look at under a mask of k bits so that its list comes out about 3/4 full
-static int64_t mrz_span_for_mask(const mrz_ctx *ctx, int64_t mask) {
-    const int k = __builtin_popcountll((unsigned long long)mask);
-    int64_t span = (ctx->cand_cap - ctx->cand_cap / 4) << (k < 24 ? k : 24);
-    if (span > ctx->seg_positions) span = ctx->seg_positions;
-    span = span / MRZ_TILE * MRZ_TILE;
-    return span < MRZ_TILE ? MRZ_TILE : span;
+// one mrz_rzip_chunk call: what its steps share besides the plan
+struct mrz_chunk_call {
+    mrz_ctx *ctx;
+    hipStream_t s;
+    const uint8_t *d_buf;
+    int64_t n;
+    int chunk_bytes;
+    hipError_t herr = hipSuccess;  // the first HIP error: sticks, and ends the call with MRZ_E_HIP
+    int rc = MRZ_OK;               // ... and the first refusal of any other kind
+    mrz_enc_totals tot;
+    uint32_t crc = 0;
+    int64_t base0 = 0, base1 = 0, lit_from = 0, n_flushes = 0;  // stream bytes so far; first literal of the next piece
+    hipEvent_t seg_ev[MRZ_SEG_AHEAD];  // one per ring slot: the launch's snapshot has arrived
+    int n_seg_ev = 0;
+    mrz_prof_spans prof;
+
+    mrz_chunk_call(mrz_ctx *c, const uint8_t *buf, int64_t bytes, int cb)
+        : ctx(c), s(c->stream), d_buf(buf), n(bytes), chunk_bytes(cb), prof(c->profiling != 0, c->stream) {
+        memset(&tot, 0, sizeof(tot));
+    }
+    bool ok() const { return herr == hipSuccess && !rc; }
+};
+// a HIP call of the chunk in flight: not made once one has failed
+#define MRZ_STEP(c, expr)                                  \
+    do {                                                   \
+        if ((c).herr == hipSuccess) (c).herr = (expr);     \
+    } while (0)
+
+// hash_search prologue (src/rzip.c:518-546): zero the table, reset state; the CRC of the chunk; the launches' events
+static void mrz_chunk_begin(mrz_chunk_call &c, mrz_seq_state *hs, int64_t victim_round, int64_t ev_cap) {
+    mrz_ctx *ctx = c.ctx;
+    memset(hs, 0, sizeof(*hs));
+    hs->n = c.n;
+    hs->end = c.n - MRZ_MIN_MATCH;
+    hs->min_mask = hs->tag_mask = (1ll << ctx->initial_freq) - 1;
+    hs->limit = ctx->nslots / 3 * 2;
+    hs->victim_round = victim_round;
+    hs->max_chain = ctx->max_chain;
+    hs->slot_mask = ctx->nslots - 1;
+    hs->event_cap = ev_cap;
+    hs->finished = hs->end > 0 ? 0 : 1;
+    MRZ_STEP(c, hipMemsetAsync(ctx->d_tab, 0, (size_t)ctx->nslots * sizeof(mrz_slot), c.s));
+    MRZ_STEP(c, hipMemcpyAsync(ctx->d_state, hs, sizeof(*hs), hipMemcpyHostToDevice, c.s));
+    MRZ_STEP(c, hipMemsetAsync(ctx->d_totals, 0, sizeof(mrz_enc_totals), c.s));
+    c.prof.begin(3);
+    MRZ_STEP(c, mrz_launch_crc32(c.s, c.d_buf, c.n, ctx->d_crc_tables, ctx->d_crc_parts, ctx->d_crc_out));
+    c.prof.end();
+    ctx->events_final = 0;
+    ctx->ev_base = 0;
+    for (int k = 0; k < MRZ_SEG_AHEAD && c.herr == hipSuccess; k++) {
+        MRZ_STEP(c, hipEventCreateWithFlags(&c.seg_ev[k], hipEventDisableTiming));
+        if (c.herr == hipSuccess) c.n_seg_ev++;
+    }
+    memset(ctx->sched_info, 0, sizeof(ctx->sched_info));
+}
+
+// ---- pieces: the matches [ctx->ev_base, upto) are encoded into the streams behind what is there and leave the list
+// (nothing is in flight: the stream holds only finished launches, and the progress hook has been shown all of them)
+static int mrz_encode_piece(mrz_chunk_call &c, int64_t upto, int final_piece) {
+    mrz_ctx *ctx = c.ctx;
+    const int64_t Ep = upto - ctx->ev_base;
+    const int64_t nblocks = (Ep + 1 + 255) / 256;
+    int r = mrz_grow(ctx, &ctx->d_block_s0, &ctx->block_cap, nblocks);
+    if (!r) r = mrz_grow(ctx, &ctx->d_block_s1, &ctx->block1_cap, nblocks);
+    if (!r) r = mrz_grow(ctx, &ctx->d_lit_off, &ctx->lit_off_cap, Ep + 2);
+    if (r) return r;
+    c.prof.begin(2);
+    MRZ_STEP(c, mrz_launch_enc_size(c.s, ctx->d_events, Ep, final_piece, c.lit_from, c.n, c.chunk_bytes, ctx->d_block_s0,
+                                    ctx->d_block_s1, c.base0, c.base1, ctx->d_totals));
+    MRZ_STEP(c, hipMemcpyAsync(&c.tot, ctx->d_totals, sizeof(c.tot), hipMemcpyDeviceToHost, c.s));
+    MRZ_STEP(c, hipStreamSynchronize(c.s));
+    if (c.herr == hipSuccess) {
+        // (a chunk without drains: the streams of the last chunk are not kept)
+        if (!c.base0) r = mrz_grow(ctx, &ctx->d_s0, &ctx->s0_cap, c.tot.s0_len + 7 + 16);
+        else r = mrz_grow_keep(ctx, &ctx->d_s0, &ctx->s0_cap, c.base0 + c.tot.s0_len + 7 + 16, c.base0);
+        if (!r && !c.base1) r = mrz_grow(ctx, &ctx->d_s1, &ctx->s1_cap, c.tot.s1_len + 16);
+        else if (!r) r = mrz_grow_keep(ctx, &ctx->d_s1, &ctx->s1_cap, c.base1 + c.tot.s1_len + 16, c.base1);
+    }
+    if (c.herr == hipSuccess && !r) {
+        MRZ_STEP(c, mrz_launch_enc_write(c.s, c.d_buf, ctx->d_events, Ep, final_piece, c.lit_from, c.n, c.chunk_bytes,
+                                         ctx->d_block_s0, ctx->d_block_s1, ctx->d_s0, ctx->d_s1, c.base1, c.tot.s1_len,
+                                         ctx->d_lit_off, ctx->d_totals, c.crc));
+        MRZ_STEP(c, hipMemcpyAsync(&c.tot, ctx->d_totals, sizeof(c.tot), hipMemcpyDeviceToHost, c.s));
+    }
+    c.prof.end();
+    return r;
+}
+
+// nothing in flight: encode what the list holds and empty it
+static int mrz_drain(mrz_chunk_call &c, mrz_chunk_plan &plan) {
+    mrz_ctx *ctx = c.ctx;
+    const int r = mrz_encode_piece(c, plan.known_events, 0);
+    if (r || c.herr != hipSuccess) return r;
+    plan.drained();
+    ctx->ev_base = plan.ev_base;
+    MRZ_STEP(c, hipMemcpyAsync(&ctx->d_state->ev_base, &ctx->ev_base, sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+    MRZ_STEP(c, hipStreamSynchronize(c.s));
+    c.base0 += c.tot.s0_len;
+    c.base1 += c.tot.s1_len;
+    c.lit_from = plan.known_last;  // (the end of the piece's last match)
+    c.n_flushes++;
+    return 0;
+}
+
+// the oldest launch's event has completed: the plan takes its snapshot, the progress hook hears of it
+static void mrz_retire(mrz_chunk_call &c, mrz_chunk_plan &plan) {
+    mrz_ctx *ctx = c.ctx;
+    const mrz_plan_news news = plan.retire(ctx->h_ring[plan.retired % MRZ_SEG_AHEAD]);
+    if (ctx->progress_fn) {
+        ctx->events_final = news.n_events;
+        if (ctx->progress_fn(ctx->progress_user, news.n_events, news.last_match, 0)) c.rc = MRZ_E_STATE;
+    }
+}
+
+static void mrz_wait_oldest(mrz_chunk_call &c, mrz_chunk_plan &plan) {
+    MRZ_STEP(c, hipEventSynchronize(c.seg_ev[plan.retired % MRZ_SEG_AHEAD]));
+    if (c.herr == hipSuccess) mrz_retire(c, plan);
+}
+
+// whatever has completed meanwhile (the engine choice and the span want the matcher's latest news) -- or, under a
+// schedule, what the schedule says
+static void mrz_retire_completed(mrz_chunk_call &c, mrz_chunk_plan &plan) {
+    const int64_t retired0 = plan.retired;
+    if (!plan.cfg.hold)
+        while (plan.retired < plan.launched && !plan.finished && !c.rc &&
+               hipEventQuery(c.seg_ev[plan.retired % MRZ_SEG_AHEAD]) == hipSuccess)
+            mrz_retire(c, plan);
+    for (const int64_t upto = plan.retired + plan.due(); plan.retired < upto && !plan.finished && c.ok();) mrz_wait_oldest(c, plan);
+    if (c.herr == hipSuccess) plan.polled(plan.retired - retired0);
+}
+
+// the candidates of the step's stretch: a front-end pass, or (window sharding) the stretch's owner scans it (with the
+// mask this rank has last heard of) and the geometry goes to the sequencer through the matcher state.  False: refused.
+static bool mrz_launch_frontend_step(mrz_chunk_call &c, mrz_chunk_plan &plan, const mrz_plan_step &st) {
+    mrz_ctx *ctx = c.ctx;
+    const int64_t end = plan.cfg.end;
+    c.prof.begin(0);
+    if (st.what == MRZ_PLAN_PASS) {
+        MRZ_STEP(c, mrz_launch_frontend(c.s, c.d_buf, c.n, ctx->d_index, ctx->d_state, (int)st.max_tiles, ctx->cand_cap,
+                                        ctx->d_fe_hdr, ctx->d_bitmap, ctx->d_tile_cnt, ctx->d_tile_off, ctx->d_grp_cnt,
+                                        ctx->d_cand));
+    } else if (!st.span) {
+        plan.stretch_ends(st.seg_start);
+    } else {
+        int64_t geo[5] = { st.seg_start, 0, 0, 0, plan.known_mask };  // seg_start, seg_end, n_cand, scan_next, list_mask
+        int64_t nx = st.seg_start, nc = 0;
+        const bool refused = c.herr == hipSuccess &&
+                             ctx->cand_fn(ctx->cand_user, st.seg_start, st.span, plan.known_mask, plan.known_p, ctx->cand_cap,
+                                          (mrz_candidate *)ctx->d_cand, ctx->d_tile_off, ctx->d_bitmap, &nx, &nc, (void *)c.s);
+        if (refused || nx <= st.seg_start || nx > st.seg_start + st.span || nx % MRZ_TILE || nc < 0 || nc > ctx->cand_cap) {
+            hipStreamSynchronize(c.s);
+            c.rc = MRZ_E_STATE;
+            return false;
+        }
+        geo[1] = nx < end + 1 ? nx : end + 1;
+        geo[2] = nc;
+        geo[3] = nx;
+        MRZ_STEP(c, hipMemcpyAsync(&ctx->d_state->seg_start, geo, sizeof(geo), hipMemcpyHostToDevice, c.s));
+        MRZ_STEP(c, hipStreamSynchronize(c.s));  // (geo lives on this stack frame)
+        plan.stretch_ends(nx);
+    }
+    c.prof.end();
+    return true;
+}
+
+// the step's engine over the list, then the launch's snapshot and event
+static void mrz_launch_sequencer_step(mrz_chunk_call &c, mrz_chunk_plan &plan, const mrz_plan_step &st) {
+    mrz_ctx *ctx = c.ctx;
+    const int helpers = ctx->farm_helpers >= 0 && ctx->farm_helpers < ctx->farm_default ? ctx->farm_helpers : ctx->farm_default;
+    const mrz_u64 *bitmap = (const mrz_u64 *)ctx->d_bitmap;
+    c.prof.begin(1);
+    if (st.engine == MRZ_ENGINE_NARROW)
+        MRZ_STEP(c, mrz_launch_sequencer_narrow(c.s, c.d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, bitmap, ctx->d_events,
+                                                ctx->d_state, ctx->d_gmailbox, helpers, ctx->xcd));
+    else if (st.engine == MRZ_ENGINE_DEEP)
+        MRZ_STEP(c, mrz_launch_sequencer_deep(c.s, c.d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, bitmap, ctx->d_events,
+                                              ctx->d_state, ctx->d_gmailbox, helpers, ctx->xcd, ctx->d_deep_shared,
+                                              ctx->deep_scanners));
+    else
+        MRZ_STEP(c, mrz_launch_sequencer(c.s, c.d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, bitmap, ctx->d_events,
+                                         ctx->d_state, ctx->d_gmailbox, helpers, ctx->d_seq_shared, ctx->d_wlog, ctx->nslots,
+                                         ctx->seq_wgs, ctx->xcd, ctx->engine_pin ? 0 : ctx->deep_min_bits));
+    c.prof.end();
+    const int slot = (int)(plan.launched % MRZ_SEG_AHEAD);
+    MRZ_STEP(c, hipMemcpyAsync(&ctx->h_ring[slot], ctx->d_state, offsetof(mrz_seq_state, prof), hipMemcpyDeviceToHost, c.s));
+    MRZ_STEP(c, hipEventRecord(c.seg_ev[slot], c.s));
+    plan.launch_queued(st);
+    // (the first two launches are waited for: the engine hint arrives early)
+    if (plan.launched <= 2 && !ctx->engine_pin && !ctx->cand_fn) MRZ_STEP(c, hipStreamSynchronize(c.s));
+}
+
+// the queued launches run out; the final matcher state, the last piece, and what the ctx reports of the chunk
+static void mrz_chunk_finish(mrz_chunk_call &c, const mrz_chunk_plan &plan, mrz_seq_state *hs) {
+    mrz_ctx *ctx = c.ctx;
+    hipStreamSynchronize(c.s);  // (also after a refusal of the progress hook: the queued launches run out)
+    for (int k = 0; k < c.n_seg_ev; k++) hipEventDestroy(c.seg_ev[k]);
+    MRZ_STEP(c, hipMemcpyAsync(hs, ctx->d_state, sizeof(*hs), hipMemcpyDeviceToHost, c.s));
+    MRZ_STEP(c, hipMemcpyAsync(&c.crc, ctx->d_crc_out, 4, hipMemcpyDeviceToHost, c.s));
+    MRZ_STEP(c, hipStreamSynchronize(c.s));
+    if (c.herr == hipSuccess) {
+        if (!c.rc && (hs->error || !hs->finished)) {
+            fprintf(stderr,
+                    "libmrzgpu: sequencer stopped abnormally: error=%d finished=%d p=%lld end=%lld events=%lld/%lld "
+                    "count=%lld min_mask=%lld scan_next=%lld launches=%lld\n",
+                    hs->error, hs->finished, (long long)hs->p, (long long)hs->end, (long long)hs->n_events,
+                    (long long)hs->event_cap, (long long)hs->count, (long long)hs->min_mask, (long long)hs->scan_next,
+                    (long long)plan.launched);
+            c.rc = MRZ_E_OVERFLOW;
+        }
+        if (!c.rc && ctx->progress_fn) {
+            ctx->events_final = hs->n_events;
+            if (ctx->progress_fn(ctx->progress_user, hs->n_events, hs->last_match, 1)) c.rc = MRZ_E_STATE;
+        }
+    }
+    // record encoding: the last piece (the whole chunk unless the list has been drained)
+    if (c.ok()) {
+        c.rc = mrz_encode_piece(c, hs->n_events, 1);
+        c.prof.end_total();
+        MRZ_STEP(c, hipStreamSynchronize(c.s));
+    }
+    ctx->timings.n_segments = (int32_t)plan.launched;
+    ctx->timings.n_narrow = (int32_t)plan.n_narrow;
+    ctx->timings.n_deep = (int32_t)plan.n_deep;
+    ctx->timings.n_event_flushes = (int32_t)c.n_flushes;
+    ctx->sched_info[0] = plan.retired;
+    ctx->sched_info[1] = plan.max_burst;
+    ctx->sched_info[2] = plan.max_lag;
+    ctx->sched_info[3] = plan.n_idle;
+    c.prof.collect(&ctx->timings);
+}
+
+// (one list for both engines and for the indices the kernels count under: mrz_seq_stats.h)
+#define MRZ_ST_NAME(id, name) name,
+static const char *const k_stat_names[MRZ_ST_N] = { MRZ_SEQ_STATS_LIST(MRZ_ST_NAME) };
+#undef MRZ_ST_NAME
+
+static void mrz_chunk_fill_result(const mrz_chunk_call &c, const mrz_seq_state &hs, mrz_chunk_result *res) {
+    mrz_ctx *ctx = c.ctx;
+    ctx->s0_len = c.base0 + c.tot.s0_len + 7;
+    ctx->s1_len = c.base1 + c.tot.s1_len;
+    ctx->have_chunk = 1;
+    res->s0_len = ctx->s0_len;
+    res->s1_len = ctx->s1_len;
+    res->crc32 = c.crc;
+    res->d_s0 = ctx->d_s0;
+    res->d_s1 = ctx->d_s1;
+    res->stats.inserts = hs.inserts;
+    res->stats.tag_hits = hs.tag_hits;
+    res->stats.tag_misses = hs.tag_misses;
+    res->stats.literals = c.tot.literals + 1;  // the zero-length terminator counts (src/rzip.c:219,664)
+    res->stats.literal_bytes = c.tot.literal_bytes;
+    res->stats.matches = c.tot.matches;
+    res->stats.match_bytes = c.tot.match_bytes;
+    res->min_mask = hs.min_mask;
+    res->hash_count = hs.count;
+    res->n_events = hs.n_events;
+    if (ctx->print_prof)
+        for (int k = 0; k < MRZ_ST_N; k++)
+            if (hs.prof[k]) fprintf(stderr, "seqstat %-12s %lld\n", k_stat_names[k], (long long)hs.prof[k]);
 }
 
 extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int where, int chunk_bytes,
@@ -515,17 +834,12 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
     memset(res, 0, sizeof(*res));
     memset(&ctx->timings, 0, sizeof(ctx->timings));
     ctx->have_chunk = 0;
-    hipStream_t s = ctx->stream;
 
     const uint8_t *d_buf = nullptr;
     int rc = mrz_stage_input(ctx, chunk, n, where, &d_buf);
     if (rc) return rc;
     rc = mrz_grow(ctx, &ctx->d_events, &ctx->event_cap, mrz_event_room(ctx, n));
     if (rc) return rc;
-    // entries the sequencers may fill (by default all the list holds); `bounded`: fewer than the chunk could emit, so the
-    // list is drained in pieces (the room rule below)
-    const int64_t ev_cap = ctx->event_cap_set > 0 ? ctx->event_cap_set : ctx->event_cap;
-    const bool bounded = ev_cap < n / MRZ_MIN_MATCH + 2;
     rc = mrz_grow(ctx, &ctx->d_crc_parts, &ctx->crc_parts_cap, mrz_crc32_parts_needed(n));
     if (rc) return rc;
     const int64_t end = n - MRZ_MIN_MATCH;  // last position that is looked up (src/rzip.c:544)
@@ -534,440 +848,50 @@ extern "C" int mrz_rzip_chunk(mrz_ctx *ctx, const void *chunk, int64_t n, int wh
         if (rc) return rc;
     }
 
-    // profiling events (optional)
-    mrz_evpair *evs = nullptr;
-    int nev = 0, evcap = 0;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    if (ctx->profiling) {
-        hipEventCreate(&ev_begin);
-        hipEventCreate(&ev_end);
-        hipEventRecord(ev_begin, s);
-    }
-#define PROF_BEGIN(k)                                                                       \
-    do {                                                                                    \
-        if (ctx->profiling) {                                                               \
-            if (nev == evcap) {                                                             \
-                const int ncap__ = evcap ? evcap * 2 : 64;                                  \
-                mrz_evpair *ne__ = (mrz_evpair *)realloc(evs, (size_t)ncap__ * sizeof(mrz_evpair)); \
-                if (ne__) evs = ne__, evcap = ncap__;                                       \
-            }                                                                               \
-            if (nev < evcap) {                                                              \
-                evs[nev].kind = (k);                                                        \
-                hipEventCreate(&evs[nev].a);                                                \
-                hipEventCreate(&evs[nev].b);                                                \
-                hipEventRecord(evs[nev].a, s);                                              \
-            }                                                                               \
-        }                                                                                   \
-    } while (0)
-#define PROF_END()                                     \
-    do {                                               \
-        if (ctx->profiling && nev < evcap) {           \
-            hipEventRecord(evs[nev].b, s);             \
-            nev++;                                     \
-        }                                              \
-    } while (0)
+    mrz_plan_config cfg;
+    cfg.end = end;
+    // entries the sequencers may fill (by default all the list holds); `bounded`: fewer than the chunk could emit, so the
+    // list is drained in pieces (the room rule of the plan)
+    cfg.ev_cap = ctx->event_cap_set > 0 ? ctx->event_cap_set : ctx->event_cap;
+    cfg.bounded = cfg.ev_cap < n / MRZ_MIN_MATCH + 2;
+    cfg.pass_cap = mrz_plan_pass_cap(cfg.ev_cap);
+    cfg.cand_cap = ctx->cand_cap;
+    cfg.seg_positions = ctx->seg_positions;
+    cfg.fe_tiles_cap = ctx->fe_tiles_cap;
+    cfg.provider = ctx->cand_fn != nullptr;
+    cfg.engine_pin = ctx->engine_pin;
+    cfg.deep_min_bits = ctx->deep_min_bits;
+    cfg.narrow_max_bits = ctx->narrow_max_bits;
+    cfg.hold = ctx->retire_hold;
+    cfg.hold_all = ctx->retire_all;
 
-    // hash_search prologue (src/rzip.c:518-546): zero the table, reset state
-    mrz_seq_state hs;
-    memset(&hs, 0, sizeof(hs));
-    hs.n = n;
-    hs.end = end;
-    hs.min_mask = hs.tag_mask = (1ll << ctx->initial_freq) - 1;
-    hs.limit = ctx->nslots / 3 * 2;
-    hs.victim_round = *victim_round;
-    hs.max_chain = ctx->max_chain;
-    hs.slot_mask = ctx->nslots - 1;
-    hs.event_cap = ev_cap;
-    hs.finished = end > 0 ? 0 : 1;
-    hipError_t herr = hipSuccess;
-    int64_t E = 0;
-    uint32_t crc = 0;
-    mrz_enc_totals tot;
-    memset(&tot, 0, sizeof(tot));
-
-#define STEP(expr)                       \
-    do {                                 \
-        if (herr == hipSuccess) herr = (expr); \
-    } while (0)
-
-    STEP(hipMemsetAsync(ctx->d_tab, 0, (size_t)ctx->nslots * sizeof(mrz_slot), s));
-    STEP(hipMemcpyAsync(ctx->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-    STEP(hipMemsetAsync(ctx->d_totals, 0, sizeof(mrz_enc_totals), s));
-
-    PROF_BEGIN(3);
-    STEP(mrz_launch_crc32(s, d_buf, n, ctx->d_crc_tables, ctx->d_crc_parts, ctx->d_crc_out));
-    PROF_END();
-
-    // ---- the segments: a front-end pass (candidate list of the next stretch) and a sequencer launch over it, again
-    // and again until the matcher reports the end of the chunk.  WHERE a pass begins and ends is device state (it goes
-    // on behind the last one, skips what an emitted match has covered, and stops where its list is full); the host
-    // only bounds the span of a pass -- from the mask the matcher has reached: the tighter the mask, the more
-    // positions a list of the same size covers -- and keeps MRZ_SEG_AHEAD segments queued.  Every launch leaves a
-    // snapshot of the matcher state in a ring of pinned host slots (ONE copy per launch: position, masks, progress and
-    // the `finished` flag belong together); the host reads a slot once the launch's event has completed.
-    ctx->events_final = 0;
-    ctx->ev_base = 0;
-    const size_t snap_bytes = offsetof(mrz_seq_state, prof);
-    hipEvent_t seg_ev[MRZ_SEG_AHEAD];
-    int n_seg_ev = 0;
-    for (int k = 0; k < MRZ_SEG_AHEAD && herr == hipSuccess; k++) {
-        STEP(hipEventCreateWithFlags(&seg_ev[k], hipEventDisableTiming));
-        if (herr == hipSuccess) n_seg_ev++;
-    }
-    int64_t launched = 0, retired = 0, n_narrow = 0, n_deep = 0;
-    int64_t span_of[MRZ_SEG_AHEAD];      // positions the pass of an in-flight launch may cover
-    int64_t known_next = 0;              // where the pass after the last retired launch begins, as far as the host knows
-    int64_t known_mask = hs.min_mask, known_p = 0;
-    int64_t hint_pos = 0, hint_matched = 0;
-    int64_t known_events = 0, known_last = 0;  // matches emitted by the last retired launch, and where the last one ended
-    bool finished = end <= 0;
-    // the retirement schedule (mrz_set_retire_schedule: a test knob; 0 = poll the events) and what mrz_schedule_info reports
-    const int hold = ctx->retire_hold, hold_all = ctx->retire_all;
-    int64_t max_burst = 0, max_lag = 0, n_idle = 0, prev_p = 0, prev_events = 0, prev_inserts = 0;
-    int64_t resume_seen = 0;  // (window sharding) launches before this one were prepared before the last resume point was known
-    memset(ctx->sched_info, 0, sizeof(ctx->sched_info));
-    // a launch whose event has completed: its snapshot is final
-    auto retire = [&]() {
-        const mrz_seq_state *sn = &ctx->h_ring[retired % MRZ_SEG_AHEAD];
-        const int64_t idx = retired++;
-        if (!sn->finished && sn->p == prev_p && sn->n_events == prev_events && sn->inserts == prev_inserts) n_idle++;
-        prev_p = sn->p, prev_events = sn->n_events, prev_inserts = sn->inserts;
-        known_p = sn->p;
-        known_mask = sn->min_mask;
-        known_events = sn->n_events;
-        known_last = sn->last_match;
-        if (!ctx->cand_fn)
-            known_next = sn->scan_next;
-        else if (sn->seg_end > sn->seg_start && sn->scan_next < sn->seg_end && idx >= resume_seen) {
-            // (window sharding, where the host drives the geometry: the wide engine has ended this launch where the mask
-            // reached the deep engine's regime and taken scan_next back to its position -- the next stretch is asked for
-            // from there.  The launches in flight right now were prepared for stretches beyond the one that was cut
-            // short: they sequence nothing and report the same resume point, which by then is old news -- a stretch from
-            // it has been queued, and known_next is where that one ends.)
-            known_next = sn->scan_next;
-            resume_seen = launched;
-        }
-        hint_pos = sn->hint_positions;
-        hint_matched = sn->hint_matched;
-        if (ctx->progress_fn) {
-            ctx->events_final = sn->n_events;
-            if (ctx->progress_fn(ctx->progress_user, sn->n_events, sn->last_match, 0)) rc = MRZ_E_STATE;
-        }
-        if (sn->finished || sn->error) finished = true;
-    };
-    // ---- pieces: the matches [ctx->ev_base, upto) are encoded into the streams behind what is there and leave the list
-    // (nothing is in flight: the stream holds only finished launches, and retire() has shown all of them to the hook)
-    int64_t base0 = 0, base1 = 0, lit_from = 0, n_flushes = 0;  // stream bytes so far; first literal of the next piece
-    auto encode_piece = [&](int64_t upto, int final_piece) {
-        const int64_t Ep = upto - ctx->ev_base;
-        const int64_t nblocks = (Ep + 1 + 255) / 256;
-        int r = mrz_grow(ctx, &ctx->d_block_s0, &ctx->block_cap, nblocks);
-        if (!r) r = mrz_grow(ctx, &ctx->d_block_s1, &ctx->block1_cap, nblocks);
-        if (!r) r = mrz_grow(ctx, &ctx->d_lit_off, &ctx->lit_off_cap, Ep + 2);
-        if (r) return r;
-        PROF_BEGIN(2);
-        STEP(mrz_launch_enc_size(s, ctx->d_events, Ep, final_piece, lit_from, n, chunk_bytes, ctx->d_block_s0,
-                                 ctx->d_block_s1, base0, base1, ctx->d_totals));
-        STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-        STEP(hipStreamSynchronize(s));
-        if (herr == hipSuccess) {
-            // (a chunk without drains: the streams of the last chunk are not kept)
-            if (!base0) r = mrz_grow(ctx, &ctx->d_s0, &ctx->s0_cap, tot.s0_len + 7 + 16);
-            else r = mrz_grow_keep(ctx, &ctx->d_s0, &ctx->s0_cap, base0 + tot.s0_len + 7 + 16, base0);
-            if (!r && !base1) r = mrz_grow(ctx, &ctx->d_s1, &ctx->s1_cap, tot.s1_len + 16);
-            else if (!r) r = mrz_grow_keep(ctx, &ctx->d_s1, &ctx->s1_cap, base1 + tot.s1_len + 16, base1);
-        }
-        if (herr == hipSuccess && !r) {
-            STEP(mrz_launch_enc_write(s, d_buf, ctx->d_events, Ep, final_piece, lit_from, n, chunk_bytes, ctx->d_block_s0,
-                                      ctx->d_block_s1, ctx->d_s0, ctx->d_s1, base1, tot.s1_len, ctx->d_lit_off,
-                                      ctx->d_totals, crc));
-            STEP(hipMemcpyAsync(&tot, ctx->d_totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-        }
-        PROF_END();
-        return r;
-    };
-    auto drain = [&]() {
-        const int r = encode_piece(known_events, 0);
-        if (r || herr != hipSuccess) return r;
-        ctx->ev_base = known_events;
-        STEP(hipMemcpyAsync(&ctx->d_state->ev_base, &ctx->ev_base, sizeof(int64_t), hipMemcpyHostToDevice, s));
-        STEP(hipStreamSynchronize(s));
-        base0 += tot.s0_len;
-        base1 += tot.s1_len;
-        lit_from = known_last;  // (the end of the piece's last match)
-        n_flushes++;
-        return 0;
-    };
-    // the span of one pass when the list is bounded: half the list's worth of positions, so that a drained list always
-    // has room for the next pass (the room rule)
-    int64_t pass_cap = MRZ_MIN_MATCH * (ev_cap / 2) / MRZ_TILE * MRZ_TILE;
-    if (pass_cap < MRZ_TILE) pass_cap = MRZ_TILE;
-    while (!finished && herr == hipSuccess && !rc) {
-        // whatever has completed meanwhile (the engine choice and the span below want the matcher's latest news)
-        const int64_t retired0 = retired;
-        if (!hold)
-            while (retired < launched && !finished && !rc && hipEventQuery(seg_ev[retired % MRZ_SEG_AHEAD]) == hipSuccess) retire();
-        else if (launched - retired >= hold) {
-            // (the schedule of mrz_set_retire_schedule: the oldest launch, or all of them, once `hold` are in flight)
-            const int64_t upto = hold_all ? launched : retired + 1;
-            while (retired < upto && !finished && !rc && herr == hipSuccess) {
-                STEP(hipEventSynchronize(seg_ev[retired % MRZ_SEG_AHEAD]));
-                if (herr == hipSuccess) retire();
-            }
-            if (herr != hipSuccess) break;
-        }
-        if (retired - retired0 > max_burst) max_burst = retired - retired0;
-        if (finished || rc) break;
-        // where the queued passes will have got to if none of them is cut short
-        int64_t est_next = known_next;
-        for (int64_t k = retired; k < launched; k++) est_next += span_of[k % MRZ_SEG_AHEAD];
-        const bool queue_full = launched - retired >= MRZ_SEG_AHEAD;
-        const bool all_queued = est_next > end;  // (only a list that fills up -- or the provider -- can prove this wrong)
-        if (queue_full || (all_queued && launched > retired)) {
-            STEP(hipEventSynchronize(seg_ev[retired % MRZ_SEG_AHEAD]));  // wait for the oldest launch
-            if (herr != hipSuccess) break;
-            retire();
-            continue;
-        }
-        if (all_queued) {
-            // nothing in flight and, by the host's book-keeping, nothing left -- yet the matcher has not reported the end:
-            // cannot happen (a pass always covers its span unless its list fills, and then known_next says so)
-            rc = MRZ_E_OVERFLOW;
-            break;
-        }
-        // ---- one more segment
-        int64_t span = mrz_span_for_mask(ctx, known_mask);
-        if (bounded && span > pass_cap) span = pass_cap;
-        int64_t max_tiles = span / MRZ_TILE;
-        if (max_tiles > ctx->fe_tiles_cap) max_tiles = ctx->fe_tiles_cap;
-        span = max_tiles * MRZ_TILE;
-        if (bounded) {
-            // The room rule: queue a pass only if the list can take every match the launches after the latest retired
-            // one (snapshot S: n_events_S matches, matcher at v = known_p) can emit.  Every position <= v has been looked
-            // at under the mask of S (a launch that used up its list leaves p at its pass's last position, lim; one that
-            // ended early, as on the wide-to-deep hand-over, leaves its real p and scan_next goes back to p's tile), and
-            // masks only tighten, so the matches emitted after S are
-            //   - the match pending in S (cur_len > 0), or a longer one that replaces it, and one match found beyond v
-            //     whose backward extension reaches before it: 2;
-            //   - matches that start at or after v: disjoint, >= 31 bytes, each emitted at a candidate -- a position of
-            //     one of the queued passes, so at or before F, the last position of the furthest one (clamped to end)
-            //     -- and starting no later than that candidate (src/rzip.c:586-599: cur_p <= p, and p returns to
-            //     last_match): at most 1 + (F - v) / 31.
-            // F is estimated from where the pass after S begins (scan_next, or the tile of v + 1 when an emitted match
-            // has carried the matcher further) plus the spans of the passes in flight.  A pass begins later than that
-            // only where a match emitted by the launch before carried p beyond its end: the positions skipped lie
-            // inside that one match, so each launch adds at most one match to the estimate -- counted below as one per
-            // launch after S.  (Passes cut short by a full candidate list, or scanned again after a hand-over, only
-            // end earlier.)  Provider mode: known_next is already where the furthest queued stretch ends.
-            const int64_t pt = (known_p + 1) / MRZ_TILE * MRZ_TILE;
-            int64_t from = known_next > pt ? known_next : pt;
-            for (int64_t k = retired; k < launched; k++) from += span_of[k % MRZ_SEG_AHEAD];
-            const int64_t fixed = known_events - ctx->ev_base + 2 + 1 + (launched - retired + 1);
-            int64_t F = from + span - 1;
-            if (F > end) F = end;
-            if (fixed + (F - known_p) / MRZ_MIN_MATCH > ev_cap) {
-                if (launched > retired) {  // wait for the oldest launch: S moves on
-                    STEP(hipEventSynchronize(seg_ev[retired % MRZ_SEG_AHEAD]));
-                    if (herr != hipSuccess) break;
-                    retire();
-                    continue;
-                }
-                if (known_events > ctx->ev_base) {  // nothing in flight: encode what the list holds and empty it
-                    rc = drain();
-                    continue;
-                }
-                // Nothing in flight and nothing to drain: shorten the pass to what fits.  No stall: here v + 1 >= the
-                // start of the pass after S less one pass at most (v is lim, or p behind a match, or p with scan_next
-                // taken back to its tile -- from is v + 1 or a tile start <= v + 1, or at most pass_cap beyond), so
-                // the room left is 31 x (ev_cap - 4) + 30 - pass_cap >= 31 x ev_cap / 2 - 94 positions: more than one
-                // tile for every capacity >= MRZ_EVENT_MIN.
-                const int64_t fit = (ev_cap - fixed) * MRZ_MIN_MATCH + MRZ_MIN_MATCH - 1 - (from - 1 - known_p);
-                if (fit < MRZ_TILE) {  // (cannot happen, see above)
-                    rc = MRZ_E_OVERFLOW;
-                    break;
-                }
-                if (span > fit) span = fit / MRZ_TILE * MRZ_TILE;
-                max_tiles = span / MRZ_TILE;
-            }
-        }
-        if (launched - retired > max_lag) max_lag = launched - retired;  // (this launch is planned on news that old)
-        PROF_BEGIN(0);
-        if (ctx->cand_fn) {
-            // window sharding: the stretch's owner scans it (with the mask this rank has last heard of); the host drives
-            // the geometry here, and hands it to the sequencer through the matcher state
-            int64_t seg_start = known_next;
-            const int64_t pt = (known_p + 1) / MRZ_TILE * MRZ_TILE;
-            if (pt > seg_start) seg_start = pt;
-            if (seg_start > end) {  // (the matcher is about to report the end)
-                known_next = seg_start;
-                span_of[launched % MRZ_SEG_AHEAD] = 0;
-            } else {
-                if (seg_start + span > end + 1) span = (end + 1 - seg_start + MRZ_TILE - 1) / MRZ_TILE * MRZ_TILE;
-                int64_t geo[5] = { seg_start, 0, 0, 0, known_mask };  // seg_start, seg_end, n_cand, scan_next, list_mask
-                int64_t nx = seg_start, nc = 0;
-                if (herr == hipSuccess && ctx->cand_fn(ctx->cand_user, seg_start, span, known_mask, known_p, ctx->cand_cap,
-                                                       (mrz_candidate *)ctx->d_cand, ctx->d_tile_off, ctx->d_bitmap, &nx, &nc,
-                                                       (void *)s)) {
-                    hipStreamSynchronize(s);
-                    rc = MRZ_E_STATE;
-                    break;
-                }
-                if (nx <= seg_start || nx > seg_start + span || nx % MRZ_TILE || nc < 0 || nc > ctx->cand_cap) {
-                    hipStreamSynchronize(s);
-                    rc = MRZ_E_STATE;
-                    break;
-                }
-                geo[1] = nx < end + 1 ? nx : end + 1;
-                geo[2] = nc;
-                geo[3] = nx;
-                STEP(hipMemcpyAsync(&ctx->d_state->seg_start, geo, sizeof(geo), hipMemcpyHostToDevice, s));
-                STEP(hipStreamSynchronize(s));  // (geo lives on this stack frame)
-                known_next = nx;
-                span_of[launched % MRZ_SEG_AHEAD] = 0;
-            }
-        } else {
-            STEP(mrz_launch_frontend(s, d_buf, n, ctx->d_index, ctx->d_state, (int)max_tiles, ctx->cand_cap, ctx->d_fe_hdr,
-                                     ctx->d_bitmap, ctx->d_tile_cnt, ctx->d_tile_off, ctx->d_grp_cnt, ctx->d_cand));
-            span_of[launched % MRZ_SEG_AHEAD] = span;
-        }
-        PROF_END();
-        // Which engine: the wide one (512 candidates per batch) unless the segments before were one long match after
-        // another (>= 80 % of the positions a launch advanced over lay inside the matches it emitted): then the
-        // narrow engine's shorter chain per match wins.  The hint lags behind like everything the host knows; the first
-        // two launches are waited for so that it arrives early.  MRZ_SEQ_ENGINE=wide|narrow pins the choice (tests,
-        // measurements).
-        const int mask_bits = __builtin_popcountll((unsigned long long)known_mask);
-        bool narrow = hint_pos > 0 && hint_matched * 10 >= hint_pos * 8 && mask_bits < ctx->narrow_max_bits;
-        // ... and the deep engine once the cull sweeps have tightened the mask: the table then consists of a few long
-        // runs (2^(hash_bits - k) of about 2/3 x 2^k slots under a k-bit mask) that every look-up reads to the end --
-        // streaming scans, not the short walks the wide engine's lanes are made for
-        bool deep = !narrow && mask_bits >= ctx->deep_min_bits;
-        if (ctx->engine_pin) narrow = ctx->engine_pin == 2, deep = ctx->engine_pin == 3;
-        const int helpers = ctx->farm_helpers >= 0 && ctx->farm_helpers < ctx->farm_default ? ctx->farm_helpers : ctx->farm_default;
-        PROF_BEGIN(1);
-        if (narrow)
-            STEP(mrz_launch_sequencer_narrow(s, d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, (const mrz_u64 *)ctx->d_bitmap,
-                                             ctx->d_events, ctx->d_state, ctx->d_gmailbox, helpers, ctx->xcd));
-        else if (deep)
-            STEP(mrz_launch_sequencer_deep(s, d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, (const mrz_u64 *)ctx->d_bitmap,
-                                           ctx->d_events, ctx->d_state, ctx->d_gmailbox, helpers, ctx->xcd, ctx->d_deep_shared,
-                                           ctx->deep_scanners));
-        else
-            STEP(mrz_launch_sequencer(s, d_buf, ctx->d_tab, ctx->d_cand, ctx->d_tile_off, (const mrz_u64 *)ctx->d_bitmap,
-                                      ctx->d_events, ctx->d_state, ctx->d_gmailbox, helpers, ctx->d_seq_shared, ctx->d_wlog,
-                                      ctx->nslots, ctx->seq_wgs, ctx->xcd, ctx->engine_pin ? 0 : ctx->deep_min_bits));
-        PROF_END();
-        if (narrow) n_narrow++;
-        if (deep) n_deep++;
-        STEP(hipMemcpyAsync(&ctx->h_ring[launched % MRZ_SEG_AHEAD], ctx->d_state, snap_bytes, hipMemcpyDeviceToHost, s));
-        STEP(hipEventRecord(seg_ev[launched % MRZ_SEG_AHEAD], s));
-        launched++;
-        if (launched <= 2 && !ctx->engine_pin && !ctx->cand_fn) STEP(hipStreamSynchronize(s));
-    }
-    hipStreamSynchronize(s);  // (also after a refusal of the progress hook: the queued launches run out)
-    for (int k = 0; k < n_seg_ev; k++) hipEventDestroy(seg_ev[k]);
-    STEP(hipMemcpyAsync(&hs, ctx->d_state, sizeof(hs), hipMemcpyDeviceToHost, s));
-    STEP(hipMemcpyAsync(&crc, ctx->d_crc_out, 4, hipMemcpyDeviceToHost, s));
-    STEP(hipStreamSynchronize(s));
-    if (herr == hipSuccess) {
-        if (!rc && (hs.error || !hs.finished)) {
-            fprintf(stderr,
-                    "libmrzgpu: sequencer stopped abnormally: error=%d finished=%d p=%lld end=%lld events=%lld/%lld "
-                    "count=%lld min_mask=%lld scan_next=%lld launches=%lld\n",
-                    hs.error, hs.finished, (long long)hs.p, (long long)hs.end, (long long)hs.n_events,
-                    (long long)hs.event_cap, (long long)hs.count, (long long)hs.min_mask, (long long)hs.scan_next,
-                    (long long)launched);
-            rc = MRZ_E_OVERFLOW;
-        }
-        E = hs.n_events;
-        if (!rc && ctx->progress_fn) {
-            ctx->events_final = E;
-            if (ctx->progress_fn(ctx->progress_user, E, hs.last_match, 1)) rc = MRZ_E_STATE;
+    mrz_chunk_call c(ctx, d_buf, n, chunk_bytes);
+    mrz_seq_state hs;  // the matcher state the chunk begins with, then the one it ends with
+    mrz_chunk_begin(c, &hs, *victim_round, cfg.ev_cap);
+    mrz_chunk_plan plan;
+    plan.init(cfg, hs.min_mask);
+    while (!plan.finished && c.ok()) {
+        mrz_retire_completed(c, plan);
+        if (plan.finished || !c.ok()) break;
+        const mrz_plan_step st = plan.next();
+        switch (st.what) {
+            case MRZ_PLAN_WAIT: mrz_wait_oldest(c, plan); break;
+            case MRZ_PLAN_DRAIN: c.rc = mrz_drain(c, plan); break;
+            case MRZ_PLAN_FAIL: c.rc = MRZ_E_OVERFLOW; break;
+            case MRZ_PLAN_PASS:
+            case MRZ_PLAN_STRETCH:
+                if (mrz_launch_frontend_step(c, plan, st)) mrz_launch_sequencer_step(c, plan, st);
+                break;
         }
     }
-
-    // record encoding: the last piece (the whole chunk unless the list has been drained)
-    if (herr == hipSuccess && !rc) {
-        rc = encode_piece(E, 1);
-        if (ctx->profiling) hipEventRecord(ev_end, s);
-        STEP(hipStreamSynchronize(s));
-    }
-
-    ctx->timings.n_segments = (int32_t)launched;
-    ctx->timings.n_narrow = (int32_t)n_narrow;
-    ctx->timings.n_deep = (int32_t)n_deep;
-    ctx->timings.n_event_flushes = (int32_t)n_flushes;
-    ctx->sched_info[0] = retired;
-    ctx->sched_info[1] = max_burst;
-    ctx->sched_info[2] = max_lag;
-    ctx->sched_info[3] = n_idle;
-    if (ctx->profiling) {
-        hipStreamSynchronize(s);
-        for (int i = 0; i < nev; i++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, evs[i].a, evs[i].b) == hipSuccess) {
-                if (evs[i].kind == 0) ctx->timings.tagscan_ms += ms;
-                if (evs[i].kind == 1) ctx->timings.sequencer_ms += ms;
-                if (evs[i].kind == 2) ctx->timings.encode_ms += ms;
-                if (evs[i].kind == 3) ctx->timings.crc_ms += ms;
-            }
-            hipEventDestroy(evs[i].a);
-            hipEventDestroy(evs[i].b);
-        }
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev_begin, ev_end) == hipSuccess) ctx->timings.total_ms = ms;
-        hipEventDestroy(ev_begin);
-        hipEventDestroy(ev_end);
-        free(evs);
-    }
-#undef PROF_BEGIN
-#undef PROF_END
-#undef STEP
-    if (herr != hipSuccess) {
-        ctx->last_err = herr;
+    mrz_chunk_finish(c, plan, &hs);
+    if (c.herr != hipSuccess) {
+        ctx->last_err = c.herr;
         return MRZ_E_HIP;
     }
-    if (rc) return rc;
-
+    if (c.rc) return c.rc;
     *victim_round = hs.victim_round;
-    ctx->s0_len = base0 + tot.s0_len + 7;
-    ctx->s1_len = base1 + tot.s1_len;
-    ctx->have_chunk = 1;
-    res->s0_len = ctx->s0_len;
-    res->s1_len = ctx->s1_len;
-    res->crc32 = crc;
-    res->d_s0 = ctx->d_s0;
-    res->d_s1 = ctx->d_s1;
-    res->stats.inserts = hs.inserts;
-    res->stats.tag_hits = hs.tag_hits;
-    res->stats.tag_misses = hs.tag_misses;
-    res->stats.literals = tot.literals + 1;  // the zero-length terminator counts (src/rzip.c:219,664)
-    res->stats.literal_bytes = tot.literal_bytes;
-    res->stats.matches = tot.matches;
-    res->stats.match_bytes = tot.match_bytes;
-    res->min_mask = hs.min_mask;
-    res->hash_count = hs.count;
-    res->n_events = E;
-    if (ctx->print_prof) {
-        // (one list for both engines: the enum of mrz_seq_common.h)
-        static const char *names[128] = { "batches", "formed", "committed", "segments", "emits", "backjump", "rewalk",
-                                          "longres", "seq_cands", "cut_cplx", "cut_overflow", "skipout", "conf0", "pairs",
-                                          "t_form", "t_walk", "t_conf", "t_pairs", "t_loop", "t_rewalk", "t_long", "t_seq",
-                                          "farmed", "l_post", "l_stripe", "l_bwd", "l_wait", "l_rounds", "f_post", "f_wait",
-                                          "f_fold", "s_tab", "s_pair", "s_ins", "ovl", "ovl_ok", "x_walk", "x_casc", "x_pool",
-                                          "x_win", "x_same", "c_win", "c_evict", "c_deep", "c_many", "c_fail", "c_tie", "c_nw", "t_ovl",
-                                          "h_pre", "h_cand", "h_post", "t_scan", "t_fold", "t_commit", "reprep", "w_stale", "w_drop", "reset",
-                                          "t_turn", "t_prep", "t_precommit", "e_mask", "e_cull", "e_xw", "e_inwin", "e_window", "e_bulk",
-                                          "e_more", "t_pc_cw", "t_pc_log", "t_pc_best", "t_pc_bulk", "t_turnwork", "t_snap", "rebulk",
-                                          "batch_lanes", "cut_long", "cut_walk", "cut_conflict", "cut_cull", "batch_emits",
-                                          "cut_cascade", "batch_formed", "t_walk2", "t_scans", "t_conflict", "t_window",
-                                          "d_batches", "d_lanes", "d_rounds", "d_rescanned", "d_coop", "d_t_form", "d_t_scan",
-                                          "d_t_commit", "d_t_rescan", "d_t_total", "d_launches", "d_t_coop", "d_coop_rec",
-                                          "d_resolved", "d_s_coop", "d_s_conflict", "d_s_culled", "d_s_nocull", "d_s_stale", "d_c_over_alt", "d_c_over_noalt", "d_c_empty",
-                                          "d_c_displace", "d_c_other" };
-        for (int k = 0; k < 128; k++)
-            if (names[k] && hs.prof[k]) fprintf(stderr, "seqstat %-12s %lld\n", names[k], (long long)hs.prof[k]);
-    }
+    mrz_chunk_fill_result(c, hs, res);
     return MRZ_OK;
 }
 

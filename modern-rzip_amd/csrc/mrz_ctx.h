@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "../../include/mrzgpu.h"
+#include "mrz_chunk_plan.h"  // MRZ_SEG_AHEAD: segment launches the host keeps queued ahead of the device
 #include "mrz_kernels.h"
 
 // One segment = one front-end pass + one sequencer launch.  A pass looks at up to MRZ_SEG_POSITIONS positions
@@ -12,7 +13,6 @@
 // (MRZ_CAND_CAP entries of 16 B): under a k-bit mask a segment covers about (3/4 cap) << k positions.
 #define MRZ_SEG_POSITIONS (1ll << 30)
 #define MRZ_CAND_CAP (8ll << 20)
-#define MRZ_SEG_AHEAD 4  // segment launches the host keeps queued ahead of the device
 
 struct mrz_ctx {
     int device;

@@ -71,25 +71,7 @@
 #ifndef MRZ_WLOG_SHIFT
 #define MRZ_WLOG_SHIFT 2
 #endif
-enum { MRZ_ST_BATCHES, MRZ_ST_FORMED, MRZ_ST_COMMITTED, MRZ_ST_SEGMENTS, MRZ_ST_EMITS, MRZ_ST_BACKJUMP, MRZ_ST_REWALK,
-       MRZ_ST_LONGRES, MRZ_ST_SEQ, MRZ_ST_CUT_CPLX, MRZ_ST_CUT_OVERFLOW, MRZ_ST_SKIPOUT, MRZ_ST_CONF0, MRZ_ST_PAIRS,
-       MRZ_ST_T_FORM, MRZ_ST_T_WALK, MRZ_ST_T_CONF, MRZ_ST_T_PAIRS, MRZ_ST_T_LOOP, MRZ_ST_T_REWALK, MRZ_ST_T_LONG,
-       MRZ_ST_T_SEQ, MRZ_ST_FARMED, MRZ_ST_L_POST, MRZ_ST_L_STRIPE, MRZ_ST_L_BWD, MRZ_ST_L_WAIT, MRZ_ST_L_ROUNDS,
-       MRZ_ST_F_POST, MRZ_ST_F_WAIT, MRZ_ST_F_FOLD, MRZ_ST_S_TAB, MRZ_ST_S_PAIR, MRZ_ST_S_INS, MRZ_ST_OVL, MRZ_ST_OVL_OK,
-       MRZ_ST_X_WALK, MRZ_ST_X_CASC, MRZ_ST_X_POOL, MRZ_ST_X_WIN, MRZ_ST_X_SAME, MRZ_ST_C_WIN, MRZ_ST_C_EVICT, MRZ_ST_C_DEEP,
-       MRZ_ST_C_MANY, MRZ_ST_C_FAIL, MRZ_ST_C_TIE, MRZ_ST_C_NW, MRZ_ST_T_OVL, MRZ_ST_H_PRE, MRZ_ST_H_CAND, MRZ_ST_H_POST,
-       MRZ_ST_T_SCAN, MRZ_ST_T_FOLD, MRZ_ST_T_COMMIT, MRZ_ST_REPREP, MRZ_ST_W_STALE, MRZ_ST_W_DROP, MRZ_ST_RESET,
-       MRZ_ST_T_TURN, MRZ_ST_T_PREP, MRZ_ST_T_PRECOMMIT, MRZ_ST_E_MASK, MRZ_ST_E_CULL, MRZ_ST_E_XW, MRZ_ST_E_INWIN,
-       MRZ_ST_E_WINDOW, MRZ_ST_E_BULK, MRZ_ST_E_MORE, MRZ_ST_T_PC_CW, MRZ_ST_T_PC_LOG, MRZ_ST_T_PC_BEST, MRZ_ST_T_PC_BULK, MRZ_ST_T_TURNWORK, MRZ_ST_T_SNAP, MRZ_ST_REBULK,
-       // (the narrow engine's own)
-       MRZ_ST_BATCH_LANES, MRZ_ST_CUT_LONG, MRZ_ST_CUT_WALK, MRZ_ST_CUT_CONFLICT, MRZ_ST_CUT_CULL, MRZ_ST_BATCH_EMITS,
-       MRZ_ST_CUT_CASCADE, MRZ_ST_BATCH_FORMED, MRZ_ST_T_WALK2, MRZ_ST_T_SCANS, MRZ_ST_T_CONFLICT, MRZ_ST_T_WINDOW,
-       // (the deep engine's own)
-       MRZ_ST_D_BATCHES, MRZ_ST_D_LANES, MRZ_ST_D_ROUNDS, MRZ_ST_D_RESCANNED, MRZ_ST_D_COOP, MRZ_ST_D_T_FORM, MRZ_ST_D_T_SCAN,
-       MRZ_ST_D_T_COMMIT, MRZ_ST_D_T_RESCAN, MRZ_ST_D_T_TOTAL, MRZ_ST_D_LAUNCHES, MRZ_ST_D_T_COOP, MRZ_ST_D_COOP_REC,
-       MRZ_ST_D_RESOLVED, MRZ_ST_D_S_COOP, MRZ_ST_D_S_CONFLICT, MRZ_ST_D_S_CULLED, MRZ_ST_D_S_NOCULL, MRZ_ST_D_S_STALE, MRZ_ST_D_C_OVER_ALT, MRZ_ST_D_C_OVER_NOALT, MRZ_ST_D_C_EMPTY, MRZ_ST_D_C_DISPLACE, MRZ_ST_D_C_OTHER,
-       MRZ_ST_N };
-static_assert(MRZ_ST_N <= (int)(sizeof(((mrz_seq_state *)0)->prof) / sizeof(int64_t)), "mrz_seq_state.prof holds the counters");
+#include "mrz_seq_stats.h"  // MRZ_ST_*: the counters and their names, one list
 
 struct mrz_seq_args {
     const uint8_t *buf;
