@@ -274,6 +274,39 @@ int mrz_lz4_compresses(mrz_ctx *ctx, const void *s_buf, int64_t s_len, int where
  * src/stream.c:1705 -- exposed for parity tests */
 int mrz_lz4_sizes(mrz_ctx *ctx, const void *const *bufs, const int *lens, int count, int where, int *sizes);
 
+/* ---- LZ4 block codec (the `-l` back-end, CTYPE_LZ4 = 5; src/stream.c:278-312 and :465-477) ----
+ * One wavefront per block, any number of blocks per call.  bufs / outs are all host or all device memory
+ * per `where` / `out_where`.  Lengths above 0x7E000000 (LZ4_MAX_INPUT_SIZE), negative lengths and null
+ * buffers with non-zero lengths give MRZ_E_ARG. */
+
+/* LZ4_compressBound: n + n/255 + 16, the capacity no input of n bytes overflows; negative for n > 0x7E000000 */
+int64_t mrz_lz4_bound(int64_t n);
+
+/* outs[i] receives the bytes liblz4 1.9.3's LZ4_compress_default(bufs[i], outs[i], lens[i], out_caps[i]) writes
+ * and out_lens[i] (host memory) what it returns: the compressed size, or 0 when the block does not fit into
+ * out_caps[i] bytes -- what lies below out_caps[i] is then unspecified.  Nothing at or beyond out_caps[i] is
+ * written.  A block may expand: only out_caps[i] >= mrz_lz4_bound(lens[i]) always fits. */
+int mrz_lz4_compress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *lens, int count, int where,
+                           void *const *outs, const int64_t *out_caps, int out_where, int64_t *out_lens);
+
+/* LZ4_decompress_safe(bufs[i], outs[i], c_lens[i], u_lens[i]) for every block.  status[i] (host memory) is 0 when
+ * block i decodes to EXACTLY u_lens[i] bytes under liblz4 1.9.3's rules (what the reference demands,
+ * src/stream.c:465-477) and MRZ_E_CORRUPT otherwise; the call itself returns MRZ_OK when it ran.  A rejected
+ * block leaves outs[i][0, u_lens[i]) unspecified; nothing outside it is written and nothing outside
+ * bufs[i][0, c_lens[i]) is read, whatever the input holds.  The rules, as liblz4's decoder applies them:
+ *   - the last sequence is literals only and ends exactly at c_lens[i]; a literal run that ends within the last
+ *     12 bytes of the output or the last 8 of the input must be that last sequence;
+ *   - a match ends at or before u_lens[i] - 5 (liblz4's one exception is kept: a sequence of at most 14 literals
+ *     and a match of at most 18 bytes at offset >= 8 that starts 32 or more bytes before the end of the output
+ *     and more than 16 before the end of the input is copied unchecked, so it may end later);
+ *   - a match-length byte may not lie in the last 5 bytes of the input; a literal-length chain stops 15 bytes
+ *     before the end of the input (without being an error there);
+ *   - decoding to fewer than u_lens[i] bytes, an offset beyond the bytes produced so far, c_lens[i] == 0: reject.
+ * ONE DELIBERATE DIFFERENCE: an offset of 0 is rejected.  liblz4 1.9.3 accepts it and copies bytes it has not
+ * written yet, so its result depends on what the output buffer held before the call. */
+int mrz_lz4_decompress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *c_lens, int count, int where,
+                             void *const *outs, const int64_t *u_lens, int out_where, int32_t *status);
+
 /* ---- BLAKE2b (co-resident checksum kernel) ------------------------------ */
 
 /* Streaming triple mirroring common/blake2b.h:47-49

@@ -60,6 +60,21 @@ int mrz_rzip_buffer(const mrz_control *control, const void *in, int64_t n, void 
                     mrz_stats *stats, uint8_t *md5_out);
 void mrz_free(void *p);
 
+/* What `mrzip -l -L<compression_level> -p<threads>` writes for a file of n bytes (file -> file): the chunk loop and
+ * sink of mrz_rzip_buffer with the LZ4 back-end behind it (compthread + lz4_compress_buf, src/stream.c:1147-1152,
+ * 278-312).  Every stream block of at least 64 bytes goes through mrz_lz4_compress_batch -- all blocks of a chunk in
+ * one launch -- and is framed {5, c_len, u_len, next} even when it expands (the reference has no size check there);
+ * smaller blocks stay CTYPE_NONE.  The block size follows open_stream_out with two buffers per thread:
+ * round_up_page(MIN(limit, MAX(limit / threads', STREAM_BUFSIZE))), limit = ramsize / 3 / 2 adjusted by the file and
+ * first-chunk size as for -n, threads' = threads + 1 when threads > 1 (src/stream.c:736,797-914).  Not modelled: the
+ * reference's fall-back to fewer threads / a smaller limit when its test malloc fails (machine dependent).
+ * compression_level 1..2 only: above that the reference calls LZ4_compress_HC -> MRZ_E_UNSUPPORTED.  magic[18] is
+ * rzip_compression_level << 4 | compression_level.  Whole-file identity with the reference's -l output is not pinned
+ * by a test (the reference binary needs liblz4's sources, which it does not vendor); its pieces are: the block
+ * payloads against liblz4 1.9.3, the streams and framing against the -n path. */
+int mrz_rzip_buffer_lz4(const mrz_control *control, int threads, const void *in, int64_t n, void **out, int64_t *out_len,
+                        mrz_stats *stats, uint8_t *md5_out);
+
 /* chunking / block sizing rules alone (src/rzip.c:875-894, src/util.c:156-176,
  * src/stream.c:797-914 for -n): returns max_chunk, *stream_bufsize optional */
 int64_t mrz_plan(const mrz_control *control, int64_t st_size, int64_t *stream_bufsize);
@@ -93,13 +108,22 @@ int mrz_rzip_pipeline(const mrz_control *control, const void *in, int64_t n, mrz
                       mrz_stats *stats, uint8_t *md5_out);
 
 /* `mrzip -d` of a whole -n archive held in memory: runzip_fd (src/runzip.c:332-437) over
- * runzip_chunk (:226-330), the block chains of the two streams (fill_buffer, src/stream.c:1412-1571;
- * CTYPE_NONE blocks only -- anything a back-end codec wrote gives MRZ_E_UNSUPPORTED) and the final
+ * runzip_chunk (:226-330), the block chains of the two streams (fill_buffer, src/stream.c:1412-1571) and the final
  * hash check (:384-412; per-chunk CRC instead when the archive carries no hash, :311-321).
+ * Blocks are CTYPE_NONE (3) or CTYPE_LZ4 (5, what `mrzip -l` writes), mixed freely.  A chunk that holds LZ4 blocks has
+ * their payloads uploaded as they are and decoded on the device (mrz_lz4_decompress_batch, one launch for the chunk)
+ * straight into the two contiguous stream buffers, CTYPE_NONE blocks copied in between, and mrz_runzip_chunk runs on
+ * that device memory: the decompressed streams do not cross the bus (exception: an archive without a size in its
+ * header, written to STDOUT in several chunks, has stream 0 fetched to size the output).  A block the decoder
+ * rejects (rules and the offset-0 difference: mrz_lz4_decompress_batch), c_len beyond the archive,
+ * c_len > u_len + u_len/255 + 16 or u_len > 255 * c_len give MRZ_E_CORRUPT; u_len > 0x7E000000, any other ctype
+ * (zstd, lzma, bzip3, zpaq) and encryption give MRZ_E_UNSUPPORTED.
  * *out is malloc'd by the library (mrz_free).  Record decoding runs on the GPU (mrz_runzip_chunk). */
 int mrz_runzip_buffer(int device, const void *mrz, int64_t n, void **out, int64_t *out_len);
 
-/* Bytes [first, first + count) of the file a -n archive decodes to, written to out_host; *file_len (may be NULL) is the
+/* CTYPE_NONE blocks only: range decode over LZ4 blocks is out of scope, an archive that holds one gets
+ * MRZ_E_UNSUPPORTED here (mrz_runzip_buffer decodes it whole).
+ * Bytes [first, first + count) of the file a -n archive decodes to, written to out_host; *file_len (may be NULL) is the
  * file's length: the header's where it carries one, otherwise the chunks are walked to the end.  Same header rules and
  * refusals as mrz_runzip_buffer (MRZ_E_UNSUPPORTED, MRZ_E_CORRUPT); first < 0, count < 0 or a range beyond the file
  * give MRZ_E_ARG, with *file_len set.  count == 0 takes out_host == NULL.

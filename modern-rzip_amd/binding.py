@@ -163,6 +163,17 @@ def load_library(path=None):
                                                  ctypes.POINTER(ci)]
         lib.mrz_lz4_compresses.argtypes = [vp, vp, i64, ci, ci, ctypes.POINTER(ci)]
         lib.mrz_lz4_sizes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ctypes.POINTER(ci)]
+    if hasattr(lib, "mrz_lz4_compress_batch"):
+        lib.mrz_lz4_bound.restype = i64
+        lib.mrz_lz4_bound.argtypes = [i64]
+        lib.mrz_lz4_compress_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci, ctypes.POINTER(vp),
+                                               ctypes.POINTER(i64), ci, ctypes.POINTER(i64)]
+        lib.mrz_lz4_decompress_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci,
+                                                 ctypes.POINTER(vp), ctypes.POINTER(i64), ci,
+                                                 ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "mrz_rzip_buffer_lz4"):
+        lib.mrz_rzip_buffer_lz4.argtypes = [ctypes.POINTER(Control), ci, vp, i64, ctypes.POINTER(vp),
+                                            ctypes.POINTER(i64), ctypes.POINTER(Stats), vp]
     if hasattr(lib, "mrz_blake2b_batch"):
         lib.mrz_blake2b_init.argtypes = [vp, ctypes.POINTER(vp), ctypes.c_size_t]
         lib.mrz_blake2b_update.argtypes = [vp, vp, ctypes.c_size_t, ci]
@@ -503,6 +514,59 @@ class RzipContext:
         _check(self.lib, self.lib.mrz_lz4_sizes(self.ctx, ptrs, lens, len(prep), prep[0][2], out), self.ctx)
         return list(out)
 
+    # ---- LZ4 block codec (the -l back-end, src/stream.c:278-312,465-477) ----
+    def _lz4_io(self, blocks, sizes, outs):
+        if not hasattr(self.lib, "mrz_lz4_compress_batch"):
+            raise MrzError("this libmrzgpu has no LZ4 block codec: rebuild it")
+        prep = [_as_ptr(b) for b in blocks]
+        n = len(prep)
+        if len(sizes) != n or (outs is not None and len(outs) != n):
+            raise MrzError("lz4: one size (and one output) per block")
+        own = outs is None
+        if own:
+            outs = [ctypes.create_string_buffer(max(1, int(c))) for c in sizes]
+            oprep = [(ctypes.cast(o, ctypes.c_void_p), len(o), MEM_HOST, o) for o in outs]
+        else:
+            oprep = [_as_ptr(o) for o in outs]
+            if any(o[1] < c for o, c in zip(oprep, sizes)):
+                raise MrzError("lz4: an output buffer is smaller than its size")
+        for group in (prep, oprep):
+            if len({g[2] for g in group}) > 1:
+                raise MrzError("lz4: the blocks (and the outputs) are all host or all device memory")
+        return (prep, oprep, outs, own,
+                (ctypes.c_void_p * n)(*[g[0] for g in prep]), (ctypes.c_int64 * n)(*[g[1] for g in prep]),
+                (ctypes.c_void_p * n)(*[g[0] for g in oprep]), (ctypes.c_int64 * n)(*[int(c) for c in sizes]))
+
+    def lz4_compress(self, blocks, caps=None, outs=None):
+        """LZ4_compress_default (liblz4 1.9.3's bytes) of every block into caps[i] bytes (default: mrz_lz4_bound).
+        Returns the payloads, b"" for a block that does not fit; with outs (writable buffers in host or device
+        memory, one per block) the bytes go there and the lengths are returned (0: does not fit)."""
+        blocks = list(blocks)
+        if not blocks:
+            return []
+        if caps is None:
+            caps = [self.lib.mrz_lz4_bound(_as_ptr(b)[1]) for b in blocks]
+        prep, oprep, outs, own, ip, il, op, ol = self._lz4_io(blocks, list(caps), outs)
+        lens = (ctypes.c_int64 * len(prep))()
+        _check(self.lib, self.lib.mrz_lz4_compress_batch(self.ctx, ip, il, len(prep), prep[0][2], op, ol, oprep[0][2],
+                                                         lens), self.ctx)
+        return [o.raw[:k] for o, k in zip(outs, lens)] if own else list(lens)
+
+    def lz4_decompress(self, blocks, u_lens, outs=None):
+        """LZ4_decompress_safe of every block to exactly u_lens[i] bytes.  Returns (payloads, statuses): status 0 or
+        MRZ_E_CORRUPT (-7) per block, the payload of a rejected block is None.  With outs (writable buffers, one
+        per block) the bytes go there and the first item is None."""
+        blocks = list(blocks)
+        if not blocks:
+            return [], []
+        prep, oprep, outs, own, ip, il, op, ol = self._lz4_io(blocks, list(u_lens), outs)
+        st = (ctypes.c_int32 * len(prep))()
+        _check(self.lib, self.lib.mrz_lz4_decompress_batch(self.ctx, ip, il, len(prep), prep[0][2], op, ol,
+                                                           oprep[0][2], st), self.ctx)
+        if not own:
+            return None, list(st)
+        return [None if s else o.raw[:int(u)] for o, u, s in zip(outs, u_lens, st)], list(st)
+
     # ---- rs-mrzip encoder (rs-mrzip/rs-mrzip.c:119-158) ----
     def rs_encode(self, data):
         ptr, n, where, keep = _as_ptr(data)
@@ -692,6 +756,29 @@ def rzip_buffer(data, level=7, window=0, unlimited=False, ramsize=60 << 30, devi
     md5 = ctypes.create_string_buffer(16)
     _check(lib, lib.mrz_rzip_buffer(ctypes.byref(ctl), ptr, n, ctypes.byref(out), ctypes.byref(out_len),
                                     ctypes.byref(st), md5))
+    try:
+        return ctypes.string_at(out, out_len.value), st, md5.raw
+    finally:
+        lib.mrz_free(out)
+
+
+def rzip_buffer_lz4(data, level=2, threads=1, window=0, unlimited=False, ramsize=60 << 30, device=0, lib=None):
+    """`mrzip -l -L<level> -p<threads>` of an in-memory file (mrz_rzip_buffer_lz4): the rzip stage of rzip_buffer with
+    every stream block of at least 64 bytes LZ4-compressed on the device.  level 1 or 2 (3.. would be LZ4 HC).
+    Returns (archive bytes, Stats, md5 bytes)."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_rzip_buffer_lz4"):
+        raise MrzError("this libmrzgpu has no mrz_rzip_buffer_lz4: rebuild it")
+    ctl = Control(level, level, window, 1 if unlimited else 0, ramsize, 4096, 1, device)
+    ptr, n, where, keep = _as_ptr(data)
+    if where != MEM_HOST:
+        raise MrzError("rzip_buffer_lz4 takes host memory")
+    out = ctypes.c_void_p()
+    out_len = ctypes.c_int64()
+    st = Stats()
+    md5 = ctypes.create_string_buffer(16)
+    _check(lib, lib.mrz_rzip_buffer_lz4(ctypes.byref(ctl), threads, ptr, n, ctypes.byref(out), ctypes.byref(out_len),
+                                        ctypes.byref(st), md5))
     try:
         return ctypes.string_at(out, out_len.value), st, md5.raw
     finally:

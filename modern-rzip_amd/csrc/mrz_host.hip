@@ -186,8 +186,18 @@ struct Sink {
         blocks = 0;
         sbuf[0].clear();
         sbuf[1].clear();
+        pending.clear();
     }
-    void emit_block(int s) {
+    // -l: the chunk's blocks wait here and go through the device compressor together when the chunk is complete
+    // (one wave per block: a batch is what keeps the device busy); the file keeps flush order all the same
+    mrz_ctx *lz4 = nullptr;
+    struct Pending {
+        int s;
+        std::vector<uint8_t> data;
+    };
+    std::vector<Pending> pending;
+
+    void put_block(int s, int ctype, const uint8_t *payload, int64_t c_len, int64_t u_len) {
         if (!blocks++) {
             out.push_back((uint8_t)cb);
             out.push_back((uint8_t)eof);
@@ -205,15 +215,60 @@ struct Sink {
         for (int i = 0; i < cb; i++)
             out[(size_t)(initial_pos + last_head[s] + i)] = (uint8_t)((uint64_t)cur_pos >> (8 * i));
         last_head[s] = cur_pos + 1 + 2 * cb;
-        const int64_t len = (int64_t)sbuf[s].size();
-        out.push_back(3);
-        put_val(len, cb);
-        put_val(len, cb);
+        out.push_back((uint8_t)ctype);
+        put_val(c_len, cb);
+        put_val(u_len, cb);
         put_val(0, cb);
         cur_pos += 1 + 3 * cb;
-        out.insert(out.end(), sbuf[s].begin(), sbuf[s].end());
-        cur_pos += len;
+        out.insert(out.end(), payload, payload + c_len);
+        cur_pos += c_len;
+    }
+    void emit_block(int s) {
+        if (lz4) {
+            pending.push_back(Pending{ s, std::vector<uint8_t>() });
+            pending.back().data.swap(sbuf[s]);
+            return;
+        }
+        const int64_t len = (int64_t)sbuf[s].size();
+        put_block(s, 3, sbuf[s].data(), len, len);
         sbuf[s].clear();
+    }
+    // compthread with LZ4_COMPRESS (src/stream.c:1147-1152): every block of at least 64 bytes is framed
+    // {CTYPE_LZ4, c_len, u_len, next} with what LZ4_compress_default makes of it, also when that is longer than the
+    // block (lz4_compress_buf, :278-312, compares nothing); its capacity there, round_up_page(n + n/16 + 67), is
+    // beyond LZ4_compressBound, so the call cannot fail.  Smaller blocks stay CTYPE_NONE.
+    int flush_lz4() {
+        std::vector<const void *> src;
+        std::vector<void *> dst;
+        std::vector<int64_t> lens, caps;
+        std::vector<std::vector<uint8_t>> packed(pending.size());
+        for (size_t i = 0; i < pending.size(); i++) {
+            const int64_t len = (int64_t)pending[i].data.size();
+            if (len < 64) continue;
+            if (len > 0x7E000000ll) return MRZ_E_UNSUPPORTED;  // LZ4_MAX_INPUT_SIZE: the reference's call returns 0
+            packed[i].resize((size_t)mrz_lz4_bound(len));
+            src.push_back(pending[i].data.data());
+            dst.push_back(packed[i].data());
+            lens.push_back(len);
+            caps.push_back((int64_t)packed[i].size());
+        }
+        std::vector<int64_t> got(src.size());
+        const int rc = mrz_lz4_compress_batch(lz4, src.data(), lens.data(), (int)src.size(), MRZ_MEM_HOST, dst.data(),
+                                              caps.data(), MRZ_MEM_HOST, got.data());
+        if (rc) return rc;
+        size_t k = 0;
+        for (size_t i = 0; i < pending.size(); i++) {
+            const int64_t len = (int64_t)pending[i].data.size();
+            if (len < 64)
+                put_block(pending[i].s, 3, pending[i].data.data(), len, len);
+            else {
+                if (got[k] <= 0) return MRZ_E_STATE;
+                put_block(pending[i].s, 5, packed[i].data(), got[k], len);
+                k++;
+            }
+        }
+        pending.clear();
+        return MRZ_OK;
     }
     void write(int s, const uint8_t *p, int64_t n) {
         while (n) {
@@ -230,7 +285,7 @@ struct Sink {
         if (rc) return rc;
         emit_block(0);  // close_stream_out flushes both, even when empty
         emit_block(1);
-        return MRZ_OK;
+        return lz4 ? flush_lz4() : MRZ_OK;
     }
 };
 
@@ -367,9 +422,31 @@ void fill_magic(uint8_t mg[20], const mrz_control *ctl, int64_t st_size) {  // w
     mg[18] = (uint8_t)((ctl->rzip_compression_level << 4) + ctl->compression_level);
 }
 
+// The stream block size of open_stream_out when a back-end compresses (src/stream.c:797-914, file -> file): two
+// buffers per thread, so limit = usable_ram / 2 where -n has usable_ram, the same two adjustments by the file and the
+// first chunk, and then the last branch of :913-914 over the thread count of prepare_streamout_threads (:736: one
+// more than -p when -p > 1).  Not modelled: the reduction of threads and the shrinking of `limit` when a test malloc
+// of limit + overhead * threads fails (:882-897) -- both depend on the machine, not on the input.
+int64_t lz4_bufsize(const mrz_control *ctl, int threads, int64_t st_size) {
+    const int64_t page = ctl->page_size > 0 ? ctl->page_size : 4096;
+    const int64_t max_chunk = mrz_plan(ctl, st_size, nullptr);
+    const int64_t first = st_size < max_chunk ? st_size : max_chunk;
+    const int64_t chunk_limit = first < page ? page : first;
+    int64_t limit = ctl->ramsize / 3 / 2;
+    if (st_size > 0 && st_size < limit)
+        limit = st_size > kStreamMin ? st_size : kStreamMin;
+    else if (limit > chunk_limit)
+        limit = chunk_limit;
+    const int64_t nthreads = threads > 1 ? threads + 1 : 1;
+    int64_t per = limit / nthreads;
+    if (per < kStreamMin) per = kStreamMin;
+    return page_ceil(limit < per ? limit : per, page);
+}
+
 // stdin_mode: 0 file (st_size known), 1 STDIN -> file, 2 STDIN -> STDOUT
+// lz4_threads: 0 = the -n sink; > 0 = the -l back-end with -p<lz4_threads> (file mode only)
 int run_chunks(const mrz_control *ctl, Source &src, int stdin_mode, int64_t st_size_known, int64_t open_chunk, Out &out,
-               mrz_stats *stats, uint8_t *md5_out) {
+               mrz_stats *stats, uint8_t *md5_out, int lz4_threads = 0) {
     const int64_t page = ctl->page_size > 0 ? ctl->page_size : 4096;
     mrz_ctx *ctx = nullptr;
     int rc = mrz_open(&ctx, ctl->device, ctl->rzip_compression_level, open_chunk);
@@ -404,9 +481,12 @@ int run_chunks(const mrz_control *ctl, Source &src, int stdin_mode, int64_t st_s
                     else if (limit > chunk_limit)
                         limit = chunk_limit;
                     bufsize = page_ceil(limit, page);
-                } else
+                } else if (lz4_threads)
+                    bufsize = lz4_bufsize(ctl, lz4_threads, st_size_known);
+                else
                     mrz_plan(ctl, st_size_known, &bufsize);
                 sink.bufsize = bufsize;
+                if (lz4_threads) sink.lz4 = ctx;
                 if (stdin_mode == 2) {
                     // STDOUT: the first block writes the magic header (src/stream.c:1202-1205); the size is only in
                     // it if the input has already ended (write_magic, src/mrzip.c:137-140)
@@ -472,12 +552,13 @@ int64_t stdin_chunk(const mrz_control *ctl, int to_stdout) {
     return max_mmap < max_chunk ? max_mmap : max_chunk;
 }
 
-int run_file(const mrz_control *ctl, const Reader &rd, int64_t n, Out &out, mrz_stats *stats, uint8_t *md5_out) {
+int run_file(const mrz_control *ctl, const Reader &rd, int64_t n, Out &out, mrz_stats *stats, uint8_t *md5_out,
+             int lz4_threads = 0) {
     int rc = check_control(ctl);
     if (rc || n < 0) return MRZ_E_ARG;
     const int64_t max_chunk = mrz_plan(ctl, n, nullptr);
     FileSource src(rd, n, max_chunk);
-    return run_chunks(ctl, src, 0, n, max_chunk < n ? max_chunk : n, out, stats, md5_out);
+    return run_chunks(ctl, src, 0, n, max_chunk < n ? max_chunk : n, out, stats, md5_out, lz4_threads);
 }
 
 int run_stdin(const mrz_control *ctl, const Reader &rd, int to_stdout, Out &out, mrz_stats *stats, uint8_t *md5_out) {
@@ -538,6 +619,27 @@ extern "C" int mrz_rzip_buffer(const mrz_control *ctl, const void *in, int64_t n
         Out o;
         o.vec = &buf;
         const int rc = run_file(ctl, rd, n, o, stats, md5_out);
+        if (rc) return rc;
+        return vec_to_malloc(buf, out, out_len);
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+}
+
+extern "C" int mrz_rzip_buffer_lz4(const mrz_control *ctl, int threads, const void *in, int64_t n, void **out,
+                                   int64_t *out_len, mrz_stats *stats, uint8_t *md5_out) {
+    if (!out || !out_len || (n > 0 && !in) || threads < 1) return MRZ_E_ARG;
+    if (check_control(ctl)) return MRZ_E_ARG;
+    if (ctl->compression_level < 1) return MRZ_E_ARG;
+    if (ctl->compression_level > 2) return MRZ_E_UNSUPPORTED;  // LZ4_compress_HC, src/stream.c:297-305
+    try {
+        std::vector<uint8_t> buf;
+        Reader rd;
+        rd.mem = (const uint8_t *)in;
+        rd.mem_n = n;
+        Out o;
+        o.vec = &buf;
+        const int rc = run_file(ctl, rd, n, o, stats, md5_out, threads);
         if (rc) return rc;
         return vec_to_malloc(buf, out, out_len);
     } catch (const std::bad_alloc &) {
@@ -869,7 +971,9 @@ int64_t peek_le(const uint8_t *p, int nbytes) {
 }
 
 // follows one stream's block chain (fill_buffer, src/stream.c:1412-1571) and hands every payload to block(p, len);
-// only CTYPE_NONE (3) blocks: the back-end codecs stay host code outside this library
+// only CTYPE_NONE (3) blocks.  This is the walk of mrz_runzip_buffer_range, which gathers bytes straight from the
+// archive's blocks: range decode over LZ4 blocks is out of scope, such an archive gets MRZ_E_UNSUPPORTED there
+// (mrz_runzip_buffer reads it: list_stream below).
 template <class F>
 int walk_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, F &&block, int64_t *end_max) {
     int64_t at = head_at;
@@ -895,6 +999,98 @@ int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t he
                   int64_t *end_max) {
     return walk_stream(mrz, n, initial_pos, head_at, cb,
                        [&](const uint8_t *p, int64_t len) { dst.insert(dst.end(), p, p + len); }, end_max);
+}
+
+// One block of a stream as mrz_runzip_buffer takes it: CTYPE_NONE (3), or CTYPE_LZ4 (5) as `mrzip -l` writes it
+// (lz4_compress_buf / lz4_decompress_buf, src/stream.c:278-312,465-477).
+struct ArcBlock {
+    int ctype;
+    const uint8_t *p;
+    int64_t c_len, u_len;
+};
+
+const int kCtypeNone = 3, kCtypeLz4 = 5;
+const int64_t kLz4MaxInput = 0x7E000000ll;
+
+// walk_stream for mrz_runzip_buffer: the chain's blocks in order, *total their decoded length
+int list_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, std::vector<ArcBlock> &blocks,
+                int64_t *total, int64_t *end_max) {
+    int64_t at = head_at;
+    *total = 0;
+    for (;;) {
+        if (at + 1 + 3 * cb > n) return MRZ_E_CORRUPT;
+        const int ctype = mrz[at];
+        const int64_t c_len = peek_le(mrz + at + 1, cb), u_len = peek_le(mrz + at + 1 + cb, cb);
+        const int64_t next = peek_le(mrz + at + 1 + 2 * cb, cb);
+        if (ctype != kCtypeNone && ctype != kCtypeLz4) return MRZ_E_UNSUPPORTED;
+        if (c_len < 0 || u_len < 0) return MRZ_E_CORRUPT;
+        if (ctype == kCtypeNone && c_len != u_len) return MRZ_E_CORRUPT;
+        const int64_t pay = at + 1 + 3 * cb;
+        if (c_len > n - pay) return MRZ_E_CORRUPT;  // (compared without adding: a length field may be 2^63 - 1)
+        if (ctype == kCtypeLz4) {
+            if (u_len > kLz4MaxInput) return MRZ_E_UNSUPPORTED;
+            // no LZ4 block is longer than LZ4_compressBound of what it holds, and none holds more than 255 bytes per
+            // byte of its own (a length byte adds at most 255): whatever claims otherwise is not worth an allocation
+            if (c_len > u_len + u_len / 255 + 16 || u_len / 255 > c_len) return MRZ_E_CORRUPT;
+        }
+        blocks.push_back(ArcBlock{ ctype, mrz + pay, c_len, u_len });
+        *total += u_len;
+        if (pay + c_len > *end_max) *end_max = pay + c_len;
+        if (!next) return MRZ_OK;
+        if (next < 0 || next > n - initial_pos || initial_pos + next <= at) return MRZ_E_CORRUPT;  // chains only run forward
+        at = initial_pos + next;
+    }
+}
+
+// The two streams of a chunk that holds LZ4 blocks, put together in device memory: CTYPE_NONE payloads are copied
+// into place, LZ4 payloads are uploaded as they are and decoded into place by mrz_lz4_decompress_batch, all blocks of
+// both streams in one launch.  What the blocks decode to never exists in host memory.
+struct DeviceStreams {
+    uint8_t *base = nullptr, *s0 = nullptr, *s1 = nullptr;
+    ~DeviceStreams() {
+        if (base) hipFree(base);
+    }
+};
+
+int build_device_streams(mrz_ctx *ctx, const std::vector<ArcBlock> (&blocks)[2], const int64_t (&total)[2],
+                         DeviceStreams &ds) {
+    int64_t packed = 0;
+    for (int s = 0; s < 2; s++)
+        for (const ArcBlock &b : blocks[s])
+            if (b.ctype == kCtypeLz4) packed += (b.c_len + 31) & ~15ll;
+    const int64_t at1 = (total[0] + 64 + 255) & ~255ll, at_packed = at1 + ((total[1] + 64 + 255) & ~255ll);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (hipMalloc((void **)&ds.base, (size_t)(at_packed + packed + 64)) != hipSuccess) return MRZ_E_NOMEM;
+    ds.s0 = ds.base;
+    ds.s1 = ds.base + at1;
+    std::vector<const void *> src;
+    std::vector<void *> dst;
+    std::vector<int64_t> c_lens, u_lens;
+    int64_t pk = at_packed;
+    for (int s = 0; s < 2; s++) {
+        uint8_t *w = s ? ds.s1 : ds.s0;
+        for (const ArcBlock &b : blocks[s]) {
+            if (b.ctype == kCtypeLz4) {
+                if (b.c_len)
+                    HIPCHK(ctx, hipMemcpyAsync(ds.base + pk, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, ctx->stream));
+                src.push_back(ds.base + pk);
+                dst.push_back(w);
+                c_lens.push_back(b.c_len);
+                u_lens.push_back(b.u_len);
+                pk += (b.c_len + 31) & ~15ll;
+            } else if (b.c_len)
+                HIPCHK(ctx, hipMemcpyAsync(w, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, ctx->stream));
+            w += b.u_len;
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> status(src.size());
+    const int rc = mrz_lz4_decompress_batch(ctx, src.data(), c_lens.data(), (int)src.size(), MRZ_MEM_DEVICE, dst.data(),
+                                            u_lens.data(), MRZ_MEM_DEVICE, status.data());
+    if (rc) return rc;
+    for (int32_t st : status)
+        if (st) return MRZ_E_CORRUPT;
+    return MRZ_OK;
 }
 
 // bytes a chunk decodes to: the lengths of its records (host side: 3 or 3 + cb bytes each); false without a terminator
@@ -960,9 +1156,35 @@ static int runzip_buffer_impl(int device, const void *mrz_v, int64_t n, void **o
         int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
         s0.clear();
         s1.clear();
-        rc = gather_stream(mrz, n, initial_pos, initial_pos, cb, s0, &end_max);
-        if (!rc) rc = gather_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, s1, &end_max);
+        std::vector<ArcBlock> blocks[2];
+        int64_t stream_len[2] = { 0, 0 };
+        rc = list_stream(mrz, n, initial_pos, initial_pos, cb, blocks[0], &stream_len[0], &end_max);
+        if (!rc) rc = list_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, blocks[1], &stream_len[1], &end_max);
         if (rc) break;
+        bool packed = false;
+        for (int s = 0; s < 2; s++)
+            for (const ArcBlock &b : blocks[s]) packed = packed || b.ctype != kCtypeNone;
+        DeviceStreams ds;
+        if (packed) {
+            if (blocks[0].size() + blocks[1].size() > 0x7fffffffu) {
+                rc = MRZ_E_UNSUPPORTED;
+                break;
+            }
+            rc = build_device_streams(ctx, blocks, stream_len, ds);
+            if (rc) break;
+            if (!size_known) {  // the one case in which stream 0 (the records, not the literals) comes back: its
+                                // records say how much room the chunk needs
+                s0.resize((size_t)stream_len[0]);
+                if (stream_len[0] &&
+                    hipMemcpy(s0.data(), ds.s0, (size_t)stream_len[0], hipMemcpyDeviceToHost) != hipSuccess) {
+                    rc = MRZ_E_HIP;
+                    break;
+                }
+            }
+        } else {
+            for (const ArcBlock &b : blocks[0]) s0.insert(s0.end(), b.p, b.p + b.c_len);
+            for (const ArcBlock &b : blocks[1]) s1.insert(s1.end(), b.p, b.p + b.c_len);
+        }
         if (!size_known) {
             int64_t need = 0;
             if (!records_out_len(s0, cb, &need)) {
@@ -981,8 +1203,12 @@ static int runzip_buffer_impl(int device, const void *mrz_v, int64_t n, void **o
         }
         int64_t got = 0;
         uint32_t crc_calc = 0, crc_stored = 0;
-        rc = mrz_runzip_chunk(ctx, s0.data(), (int64_t)s0.size(), s1.data(), (int64_t)s1.size(), MRZ_MEM_HOST, cb,
-                              res + total, MRZ_MEM_HOST, cap - total, &got, &crc_calc, &crc_stored);
+        if (packed)
+            rc = mrz_runzip_chunk(ctx, ds.s0, stream_len[0], ds.s1, stream_len[1], MRZ_MEM_DEVICE, cb, res + total,
+                                  MRZ_MEM_HOST, cap - total, &got, &crc_calc, &crc_stored);
+        else
+            rc = mrz_runzip_chunk(ctx, s0.data(), (int64_t)s0.size(), s1.data(), (int64_t)s1.size(), MRZ_MEM_HOST, cb,
+                                  res + total, MRZ_MEM_HOST, cap - total, &got, &crc_calc, &crc_stored);
         if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // more output than the header promised
         if (rc) break;
         if (!hash_code && crc_calc != crc_stored) {  // "Bad checksum", src/runzip.c:317-320 (only without a hash)

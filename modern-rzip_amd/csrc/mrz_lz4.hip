@@ -1,4 +1,5 @@
-// mrz_lz4.hip -- the per-block LZ4 compressibility gate.
+// mrz_lz4.hip -- the per-block LZ4 compressibility gate, and the LZ4 block codec (the -l back-end) further down:
+// the same compressor with its bytes written out, and LZ4_decompress_safe as one wave per block.
 //
 // Replaces lz4_compresses (src/stream.c:1685-1733), which asks "what would
 // LZ4_compress_default(buf, tmp, in_len, in_len + 1) return?" for a growing
@@ -22,6 +23,9 @@
 //
 // Bound: latency of dependent L2 reads per match; HBM traffic = bytes tested.
 #include <string.h>
+
+#include <new>
+#include <vector>
 
 #include "mrz_ctx.h"
 #include "mrz_device.h"
@@ -72,9 +76,34 @@ __device__ static int64_t mrz_lz_count(const uint8_t *src, int64_t a, int64_t b,
     }
 }
 
-// what LZ4_compress_default(src, dst, n, cap) returns (0 = does not fit)
-__device__ static int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, int cap, uint32_t *tab, int lane) {
-    if (n <= 0) return n == 0 && cap > 0 ? 1 : 0;
+__device__ __forceinline__ void mrz_st16(uint8_t *p, uint4 v) { __builtin_memcpy(p, &v, 16); }
+
+// dst[0, len) = src[0, len), the ranges apart: 64 lanes x 16 B, then the last len % 16 bytes one per lane
+__device__ static void mrz_lz_copy(uint8_t *dst, const uint8_t *src, int64_t len, int lane) {
+    for (int64_t off = (int64_t)lane * 16; off + 16 <= len; off += 1024) mrz_st16(dst + off, mrz_ld16(src + off));
+    const int64_t t = (len & ~15ll) + lane;
+    if (t < len) dst[t] = src[t];
+}
+
+// the bytes that follow a 15 in a token nibble: (rest / 255) times 255, then rest % 255
+__device__ static void mrz_lz_put_len(uint8_t *dst, int64_t rest, int lane) {
+    const int64_t full = rest / 255;
+    for (int64_t j = lane; j < full; j += 64) dst[j] = 255;
+    if (lane == 0) dst[full] = (uint8_t)(rest - full * 255);
+}
+
+// what LZ4_compress_default(src, dst, n, cap) returns (0 = does not fit).  EMIT = false only counts (the gate and
+// mrz_lz4_sizes: `dst` is not touched); EMIT = true also writes liblz4 1.9.3's bytes, every store below dst + cap
+// (each follows the `limited` check that liblz4 itself relies on to stay inside the buffer).
+template <bool EMIT>
+__device__ static int mrz_lz4_wave(const uint8_t *__restrict__ src, int n, int cap, uint32_t *tab, int lane,
+                                   uint8_t *__restrict__ dst) {
+    if (n <= 0) {
+        if (n < 0 || cap <= 0) return 0;
+        if constexpr (EMIT)
+            if (lane == 0) dst[0] = 0;
+        return 1;
+    }
     const bool limited = cap < n + n / 255 + 16;
     const bool small = n < MRZ_LZ_64K_LIMIT;
     for (int i = lane; i < 8192; i += 64) tab[i] = 0;
@@ -82,6 +111,8 @@ __device__ static int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, 
     const int64_t mlimit = (int64_t)n - MRZ_LZ_LASTLITERALS;
     const int64_t olimit = cap;
     int64_t ip = 0, anchor = 0, op = 0;
+    int64_t tok = 0;  // EMIT: where the current sequence's token goes, and its literal nibble
+    int tok_lit = 0;
     bool to_tail = n < MRZ_LZ_MINLEN;
 
     if (!to_tail) {
@@ -170,17 +201,32 @@ __device__ static int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, 
         // ---- literal run accounting ---------------------------------------
         {
             const int64_t lit = ip - anchor;
+            tok = op;
             op += 1;  // token
             if (limited && op + lit + (2 + 1 + MRZ_LZ_LASTLITERALS) + lit / 255 > olimit) return 0;
+            if constexpr (EMIT) {
+                tok_lit = lit < 15 ? (int)lit : 15;
+                if (lit >= 15) mrz_lz_put_len(dst + op, lit - 15, lane);
+            }
             if (lit >= 15) op += (lit - 15) / 255 + 1;
+            if constexpr (EMIT) mrz_lz_copy(dst + op, src + anchor, lit, lane);
             op += lit;
         }
         // ---- match(es): _next_match loop ------------------------------------
         while (true) {
+            if constexpr (EMIT)
+                if (lane == 0) {
+                    dst[op] = (uint8_t)(ip - match);
+                    dst[op + 1] = (uint8_t)((ip - match) >> 8);
+                }
             op += 2;  // offset
             int64_t mc = mrz_lz_count(src, ip + 4, match + 4, mlimit, lane);
             ip += mc + 4;
             if (limited && op + (1 + MRZ_LZ_LASTLITERALS) + (mc + 240) / 255 > olimit) return 0;
+            if constexpr (EMIT) {
+                if (lane == 0) dst[tok] = (uint8_t)(tok_lit << 4 | (mc < 15 ? (int)mc : 15));
+                if (mc >= 15) mrz_lz_put_len(dst + op, mc - 15, lane);
+            }
             if (mc >= 15) {
                 mc -= 15;
                 op += mc / 255 + 1;
@@ -201,6 +247,8 @@ __device__ static int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, 
             }
             mi = (uint32_t)mrz_lane_read((int)mi, 0);
             if ((small || (int64_t)mi + MRZ_LZ_MAXDIST >= ip) && mrz_ld4(src + mi) == mrz_ld4(src + ip)) {
+                tok = op;
+                tok_lit = 0;
                 op += 1;  // token of a zero-literal sequence
                 match = mi;
                 continue;
@@ -212,10 +260,20 @@ __device__ static int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, 
     // ---- last literals ------------------------------------------------------
     const int64_t last = (int64_t)n - anchor;
     if (limited && op + last + 1 + (last + 255 - 15) / 255 > olimit) return 0;
+    if constexpr (EMIT) {
+        if (lane == 0) dst[op] = (uint8_t)((last < 15 ? (int)last : 15) << 4);
+        if (last >= 15) mrz_lz_put_len(dst + op + 1, last - 15, lane);
+    }
     op += 1;
     if (last >= 15) op += (last - 15) / 255 + 1;
+    if constexpr (EMIT) mrz_lz_copy(dst + op, src + anchor, last, lane);
     op += last;
     return (int)op;
+}
+
+__device__ __forceinline__ int mrz_lz4_size_wave(const uint8_t *__restrict__ src, int n, int cap, uint32_t *tab,
+                                                 int lane) {
+    return mrz_lz4_wave<false>(src, n, cap, tab, lane, nullptr);
 }
 
 // sizes[i] = LZ4_compress_default size of block i with dst capacity lens[i] + 1
@@ -255,6 +313,143 @@ __global__ __launch_bounds__(64) void mrz_lz4_gate_kernel(const uint8_t *const *
         }
     }
     if (threadIdx.x == 0) results[i] = (int)(pct > threshold ? 0 : pct < 1 ? pct + 1 : pct);
+}
+
+// outs[i][0, out_lens[i]) = LZ4_compress_default(bufs[i], lens[i]) into caps[i] bytes; out_lens[i] = 0: does not fit
+__global__ __launch_bounds__(64) void mrz_lz4_compress_kernel(const uint8_t *const *__restrict__ bufs,
+                                                              const int64_t *__restrict__ lens,
+                                                              uint8_t *const *__restrict__ outs,
+                                                              const int64_t *__restrict__ caps, int count,
+                                                              int64_t *__restrict__ out_lens) {
+    __shared__ uint32_t tab[8192];
+    const int i = blockIdx.x;
+    if (i >= count) return;
+    const int n = (int)lens[i];
+    const int64_t bound = (int64_t)n + n / 255 + 16;  // a larger capacity changes nothing
+    const int cap = (int)(caps[i] < bound ? caps[i] : bound);
+    const int r = mrz_lz4_wave<true>(bufs[i], n, cap, tab, threadIdx.x, outs[i]);
+    if (threadIdx.x == 0) out_lens[i] = r;
+}
+
+// ---- decoder ---------------------------------------------------------------------
+// LZ4_decompress_safe(src, dst, c_len, u_len) of liblz4 1.9.3 as one wave: the sequences are walked one after the
+// other (every value that steers the walk is wave-uniform), the copies are wave-wide.  Returns 0 iff liblz4 would
+// return u_len, with one deliberate difference: an offset of 0 is a reject (liblz4 copies bytes it has not written).
+// The accept rules are those of liblz4's loop, line by line, its `shortcut` included -- it is the one place where a
+// match may end inside the last 5 bytes.  Independently of them no load leaves [src, src + c_len) and no store leaves
+// [dst, dst + u_len): every length is compared with what is left of both buffers before it is used.
+//
+// A match reads bytes that this wave stored for earlier sequences, possibly the previous instruction's.  The stores
+// of one wave are ordered before its later loads by the workgroup barrier (vmcnt(0) + s_barrier; the block is this one
+// wave), as in mrz_uz_decode_kernel; `synced` skips the barrier when the source lies in bytes that are ordered already.
+__device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64_t c_len, uint8_t *dst, int64_t u_len,
+                                          int lane) {
+    if (c_len <= 0 || u_len < 0) return 1;
+    if (u_len == 0) return c_len == 1 && src[0] == 0 ? 0 : 1;
+    int64_t ip = 0, op = 0, synced = 0;
+    while (true) {
+        if (ip >= c_len) return 1;
+        const int token = mrz_uni(src[ip]);
+        ip++;
+        int64_t lit = token >> 4;
+        int64_t ml = token & 15;
+        int64_t offset;
+        bool checked = false;  // the shortcut: 0..14 literals and a short match far from both ends
+        if (lit != 15 && ip < c_len - 16 && op <= u_len - 32) {
+            for (int64_t j = lane; j < lit; j += 64) dst[op + j] = src[ip + j];
+            ip += lit;
+            op += lit;
+            offset = mrz_uni((int)src[ip] | (int)src[ip + 1] << 8);
+            ip += 2;
+            checked = ml != 15 && offset >= 8 && offset <= op;
+        } else {
+            if (lit == 15) {  // 255 255 .. x; liblz4 stops reading 15 bytes before the end without calling it an error
+                const int64_t stop_at = c_len - 15;
+                if (ip >= stop_at) return 1;
+                while (true) {
+                    const int64_t pos = ip + lane;
+                    const bool valid = pos < stop_at;
+                    const int b = valid ? src[pos] : 0;
+                    const mrz_u64 stop = __ballot(b != 255);
+                    if (!stop) {
+                        lit += 255 * 64;
+                        ip += 64;
+                        continue;
+                    }
+                    const int f = __ffsll((long long)stop) - 1;
+                    lit += 255 * f;
+                    ip += f;
+                    if (ip < stop_at) {
+                        lit += mrz_lane_read(b, f);
+                        ip++;
+                    }
+                    break;
+                }
+            }
+            if (lit > c_len - ip || lit > u_len - op) return 1;
+            if (op + lit > u_len - 12 || ip + lit > c_len - 8) {  // must be the last sequence
+                if (ip + lit != c_len) return 1;
+                mrz_lz_copy(dst + op, src + ip, lit, lane);
+                return op + lit == u_len ? 0 : 1;
+            }
+            mrz_lz_copy(dst + op, src + ip, lit, lane);
+            ip += lit;
+            op += lit;
+            offset = mrz_uni((int)src[ip] | (int)src[ip + 1] << 8);
+            ip += 2;
+        }
+        if (ml == 15) {  // liblz4 refuses a length byte among the last 5 bytes, the closing one included
+            const int64_t stop_at = c_len - 5;
+            while (true) {
+                const int64_t pos = ip + lane;
+                const bool valid = pos < stop_at;
+                const int b = valid ? src[pos] : 0;
+                const mrz_u64 stop = __ballot(b != 255);
+                if (!stop) {
+                    ml += 255 * 64;
+                    ip += 64;
+                    continue;
+                }
+                const int f = __ffsll((long long)stop) - 1;
+                if (ip + f >= stop_at) return 1;
+                ml += 255 * f + mrz_lane_read(b, f);
+                ip += f + 1;
+                break;
+            }
+        }
+        ml += 4;
+        if (offset == 0 || offset > op) return 1;
+        if (ml > u_len - op) return 1;
+        if (!checked && op + ml > u_len - 5) return 1;
+        const int64_t from = op - offset;
+        if ((offset < ml ? op : from + ml) > synced) {
+            __syncthreads();
+            synced = op;
+        }
+        if (offset >= ml)
+            mrz_lz_copy(dst + op, dst + from, ml, lane);
+        else {  // periodic: every byte comes from the first period, which is stored and ordered
+            const int period = (int)offset, step = 64 % period;
+            int idx = lane % period;
+            for (int64_t j = lane; j < ml; j += 64) {
+                dst[op + j] = dst[from + idx];
+                idx += step;
+                if (idx >= period) idx -= period;
+            }
+        }
+        op += ml;
+    }
+}
+
+__global__ __launch_bounds__(64) void mrz_lz4_decode_kernel(const uint8_t *const *__restrict__ bufs,
+                                                            const int64_t *__restrict__ c_lens,
+                                                            uint8_t *const *__restrict__ outs,
+                                                            const int64_t *__restrict__ u_lens, int count,
+                                                            int *__restrict__ status) {
+    const int i = blockIdx.x;
+    if (i >= count) return;
+    const int r = mrz_lz4_decode_wave(bufs[i], c_lens[i], outs[i], u_lens[i], threadIdx.x);
+    if (threadIdx.x == 0) status[i] = r ? MRZ_E_CORRUPT : 0;
 }
 
 // ---- host side -----------------------------------------------------------------
@@ -362,5 +557,161 @@ extern "C" int mrz_lz4_sizes(mrz_ctx *ctx, const void *const *bufs, const int *l
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(sizes, d_res, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MRZ_OK;
+}
+
+// ---- the block codec ---------------------------------------------------------------
+extern "C" int64_t mrz_lz4_bound(int64_t n) {
+    if (n < 0 || n > 0x7E000000ll) return -1;
+    return n + n / 255 + 16;
+}
+
+// scratch of at least `need` bytes (contents are not kept)
+static int mrz_lz4_reserve(mrz_ctx *ctx, int64_t need) {
+    if (need <= ctx->lz4_scratch_cap && ctx->lz4_scratch) return MRZ_OK;
+    if (ctx->lz4_scratch) hipFree(ctx->lz4_scratch);
+    ctx->lz4_scratch = nullptr;
+    ctx->lz4_scratch_cap = 0;
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)need) != hipSuccess) return MRZ_E_NOMEM;
+    ctx->lz4_scratch = p;
+    ctx->lz4_scratch_cap = need;
+    return MRZ_OK;
+}
+
+// Shared by both directions.  scratch layout: in ptrs | in lens | out ptrs | out lens | results (8 B per block each)
+// | staged inputs (where == host) | staged outputs (out_where == host), every block on a 16-byte boundary.
+// in_lens[i] bytes are read from bufs[i]; out_room[i] bytes may be written at outs[i].
+struct mrz_lz4_job {
+    uint8_t *base;
+    int64_t in_at, out_at;
+    std::vector<const uint8_t *> in_ptr;
+    std::vector<uint8_t *> out_ptr;
+};
+
+static int mrz_lz4_stage(mrz_ctx *ctx, mrz_lz4_job &job, const void *const *bufs, const int64_t *in_lens, int count,
+                         int where, void *const *outs, const int64_t *out_room, int out_where) {
+    int64_t in_total = 0, out_total = 0;
+    for (int i = 0; i < count; i++) {
+        in_total += (in_lens[i] + 31) & ~15ll;
+        out_total += (out_room[i] + 31) & ~15ll;
+    }
+    const int64_t hdr = (int64_t)count * 40;
+    job.in_at = (hdr + 15) & ~15ll;
+    job.out_at = job.in_at + (where == MRZ_MEM_HOST ? in_total : 0);
+    const int rc = mrz_lz4_reserve(ctx, job.out_at + (out_where == MRZ_MEM_HOST ? out_total : 0) + 64);
+    if (rc) return rc;
+    job.base = (uint8_t *)ctx->lz4_scratch;
+    job.in_ptr.resize((size_t)count);
+    job.out_ptr.resize((size_t)count);
+    hipError_t e = hipSuccess;
+    int64_t in_off = job.in_at, out_off = job.out_at;
+    for (int i = 0; i < count && e == hipSuccess; i++) {
+        if (where == MRZ_MEM_HOST) {
+            job.in_ptr[(size_t)i] = job.base + in_off;
+            if (in_lens[i])
+                e = hipMemcpyAsync(job.base + in_off, bufs[i], (size_t)in_lens[i], hipMemcpyHostToDevice, ctx->stream);
+            in_off += (in_lens[i] + 31) & ~15ll;
+        } else
+            job.in_ptr[(size_t)i] = (const uint8_t *)bufs[i];
+        if (out_where == MRZ_MEM_HOST) {
+            job.out_ptr[(size_t)i] = job.base + out_off;
+            out_off += (out_room[i] + 31) & ~15ll;
+        } else
+            job.out_ptr[(size_t)i] = (uint8_t *)outs[i];
+    }
+    const size_t col = (size_t)count * 8;
+    if (e == hipSuccess) e = hipMemcpyAsync(job.base, job.in_ptr.data(), col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(job.base + col, in_lens, col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(job.base + 2 * col, job.out_ptr.data(), col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(job.base + 3 * col, out_room, col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host arrays are the caller's and ours
+    if (e != hipSuccess) {
+        ctx->last_err = e;
+        return MRZ_E_HIP;
+    }
+    return MRZ_OK;
+}
+
+static int mrz_lz4_batch_args(mrz_ctx *ctx, const void *const *bufs, const int64_t *a, int count, int where,
+                              void *const *outs, const int64_t *b, int out_where, const void *res) {
+    if (!ctx || count < 0 || (count && (!bufs || !a || !outs || !b || !res))) return MRZ_E_ARG;
+    if (where != MRZ_MEM_HOST && where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
+    if (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE) return MRZ_E_ARG;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_lz4_compress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *lens, int count, int where,
+                                      void *const *outs, const int64_t *out_caps, int out_where, int64_t *out_lens) {
+    int rc = mrz_lz4_batch_args(ctx, bufs, lens, count, where, outs, out_caps, out_where, out_lens);
+    if (rc) return rc;
+    if (!count) return MRZ_OK;
+    try {
+        // no block needs more than mrz_lz4_bound(n) bytes: stage (and let the kernel see) no more than that
+        std::vector<int64_t> room((size_t)count);
+        for (int i = 0; i < count; i++) {
+            if (lens[i] < 0 || lens[i] > 0x7E000000ll || (lens[i] && !bufs[i])) return MRZ_E_ARG;
+            if (out_caps[i] < 0 || (out_caps[i] && !outs[i])) return MRZ_E_ARG;
+            const int64_t bound = mrz_lz4_bound(lens[i]);
+            room[(size_t)i] = out_caps[i] < bound ? out_caps[i] : bound;
+        }
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        mrz_lz4_job job;
+        rc = mrz_lz4_stage(ctx, job, bufs, lens, count, where, outs, room.data(), out_where);
+        if (rc) return rc;
+        const size_t col = (size_t)count * 8;
+        int64_t *d_res = (int64_t *)(job.base + 4 * col);
+        hipLaunchKernelGGL(mrz_lz4_compress_kernel, dim3((unsigned)count), dim3(64), 0, ctx->stream,
+                           (const uint8_t *const *)job.base, (const int64_t *)(job.base + col),
+                           (uint8_t *const *)(job.base + 2 * col), (const int64_t *)(job.base + 3 * col), count, d_res);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(out_lens, d_res, col, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (out_where == MRZ_MEM_HOST) {
+            for (int i = 0; i < count; i++)
+                if (out_lens[i] > 0)
+                    HIPCHK(ctx, hipMemcpyAsync(outs[i], job.out_ptr[(size_t)i], (size_t)out_lens[i],
+                                               hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+    return MRZ_OK;
+}
+
+extern "C" int mrz_lz4_decompress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *c_lens, int count,
+                                        int where, void *const *outs, const int64_t *u_lens, int out_where,
+                                        int32_t *status) {
+    int rc = mrz_lz4_batch_args(ctx, bufs, c_lens, count, where, outs, u_lens, out_where, status);
+    if (rc) return rc;
+    if (!count) return MRZ_OK;
+    try {
+        for (int i = 0; i < count; i++) {
+            if (c_lens[i] < 0 || c_lens[i] > 0x7E000000ll || (c_lens[i] && !bufs[i])) return MRZ_E_ARG;
+            if (u_lens[i] < 0 || u_lens[i] > 0x7E000000ll || (u_lens[i] && !outs[i])) return MRZ_E_ARG;
+        }
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        mrz_lz4_job job;
+        rc = mrz_lz4_stage(ctx, job, bufs, c_lens, count, where, outs, u_lens, out_where);
+        if (rc) return rc;
+        const size_t col = (size_t)count * 8;
+        int *d_res = (int *)(job.base + 4 * col);
+        hipLaunchKernelGGL(mrz_lz4_decode_kernel, dim3((unsigned)count), dim3(64), 0, ctx->stream,
+                           (const uint8_t *const *)job.base, (const int64_t *)(job.base + col),
+                           (uint8_t *const *)(job.base + 2 * col), (const int64_t *)(job.base + 3 * col), count, d_res);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(status, d_res, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (out_where == MRZ_MEM_HOST) {  // a rejected block's bytes are unspecified: they stay on the device
+            for (int i = 0; i < count; i++)
+                if (!status[i] && u_lens[i])
+                    HIPCHK(ctx, hipMemcpyAsync(outs[i], job.out_ptr[(size_t)i], (size_t)u_lens[i],
+                                               hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
     return MRZ_OK;
 }
