@@ -59,6 +59,21 @@
 #else
 #define MRZ_DEEP_WAIT() ((void)0)
 #endif
+// the split of the SCAN phase's cycles (-DMRZ_SEQ_PROFILE): a timer of its own beside PROF_ADD's, which keeps the phase's total
+#ifdef MRZ_SEQ_PROFILE
+#define DPROF_T0() int64_t dprof_t0 = (int64_t)__builtin_amdgcn_s_memtime()
+#define DPROF_T0R() dprof_t0 = (int64_t)__builtin_amdgcn_s_memtime()
+#define DPROF_ADD(acc)                                               \
+    do {                                                             \
+        const int64_t now__ = (int64_t)__builtin_amdgcn_s_memtime(); \
+        (acc) += now__ - dprof_t0;                                   \
+        dprof_t0 = now__;                                            \
+    } while (0)
+#else
+#define DPROF_T0()
+#define DPROF_T0R()
+#define DPROF_ADD(acc)
+#endif
 #define MRZ_DEEP_MAP 2048      // entries of the two maps of planned writes (slots, tags)
 #define MRZ_DEEP_CW_WORDS 32   // cull window: 32 x 64 slots ahead of tag_clean_ptr
 #define MRZ_DEEP_XW 192        // slots written by cooperative-path candidates inside one batch (beyond: the batch is cut)
@@ -473,11 +488,12 @@ __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, i
 // ANY blocks but the committer's, on all eight XCDs -- take a share of every batch's lanes: the committer posts the batch
 // (positions, tags, masks) in device memory, every helper scans the lanes dealt to it into its own LDS and copies the
 // records out; the committer scans its own share meanwhile, waits for the helpers' lanes and copies their records in.
-// The XCDs' L2s are not coherent with each other, so everything that crosses travels release -> flag -> acquire at
-// agent scope: the committer's table stores of the commits before (every wave's vmcnt(0), a barrier, ONE release fence =
-// the write-back of its XCD's L2) before the batch's sequence number is stored; a helper's acquire fence (its L1 and its
-// XCD's L2 give up what they held) after it has seen the number and before it reads the job or the table; the same the
-// other way round for the records.  What a helper reads of the table is then the state at the post -- the state the
+// The XCDs' L2s are not coherent with each other, so what goes down travels release -> flag -> acquire at agent scope:
+// the committer's table stores of the commits before (every wave's vmcnt(0), a barrier, ONE release fence = the
+// write-back of its XCD's L2) before the batch's sequence number is stored; a helper's acquire fence (its L1 and its
+// XCD's L2 give up what they held) after it has seen the number and before it reads the job or the table.  The records
+// come back as packed 16-byte granules, stored write-through and loaded past the L1 (below, with mrz_deep_shared).
+// What a helper reads of the table is then the state at the post -- the state the
 // committer's own scan sees --, and the table is not written again before the batch's lanes are all back.
 // Rescans, conflicts and the commit stay the committer's.  A helper that is not there (not resident, another XCD, a
 // launch without spare blocks) is simply not dealt any lanes: helpers check in with a ticket and the committer counts
@@ -485,11 +501,54 @@ __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, i
 #ifndef MRZ_DEEP_SCANNERS
 #define MRZ_DEEP_SCANNERS 63
 #endif
+#define MRZ_DEEP_STAMP_RETRIES (1 << 20)  // looks a helper takes at a job line that is being rewritten before it gives up
 #ifndef MRZ_DEEP_HELP_MIN
 #define MRZ_DEEP_HELP_MIN 48  // lanes a batch must have before it is dealt out
 #endif
 
-struct mrz_deep_shared {  // device memory, zeroed by the host before every launch
+// The hand-off, as built (the forms and their conditions: release / acquire at agent scope, and write-through stores read
+// back by cache-bypassing loads):
+//   job down    every committer wave's vmcnt(0), a barrier, ONE release fence + vmcnt(0) of lane 0, then a relaxed store of
+//               `seq`.  A helper polls `seq` relaxed, then ONE acquire fence, vmcnt(0) (the invalidate has completed before
+//               the barrier lets the other waves load), a barrier, plain loads of job, q / t and table.
+//   job stamp   {job_seq, nb, nscan} are ONE 16-byte granule (one store, one load).  A helper works on a batch only if the
+//               stamp it read with nb / nscan is the `seq` it polled: a helper that checked in after the committer counted
+//               the helpers of batch N may read the job line while batch N + 1 is being written, and then sees either
+//               N's granule (nscan does not include it: nothing to do) or N + 1's (stamp != seq: it polls again, `seen`
+//               unchanged).  A helper that is counted reads a line the committer does not touch before its lanes are back.
+//   records up  the wave that scanned a lane packs its record into 16-byte granules and stores them with ONE write-through
+//               (sc1) store instruction; every storing wave's vmcnt(0), a barrier, ONE lane's relaxed agent-scope add to
+//               `done`.  `done` only grows over a launch (the committer keeps the running target), so an add never counts
+//               for another batch.  The committer polls `done` relaxed (an sc1 load), a barrier, then every wave loads
+//               its share of the records with sc1 buffer loads (past the L1: no acquire fence) and unpacks them to LDS.
+//               The records are in hipMalloc'd memory and the kernel's LDS admits one workgroup per CU, as that form needs.
+//   -DMRZ_DEEP_HANDOFF_FENCED keeps the layout and takes the fenced form for the records too: plain stores, ONE release
+//   fence + vmcnt(0) before the add, ONE acquire fence + vmcnt(0) before the barrier, plain loads.
+#define MRZ_DEEP_REC_HDR 5                                  // granules of a record's header
+#define MRZ_DEEP_REC_GRANULES (MRZ_DEEP_REC_HDR + MRZ_SMAX)  // ... and one per tag-equal entry
+struct mrz_deep_rec_ent {
+    int64_t same_off;
+    int same_slot;
+    unsigned short raw, pad;
+};
+struct __attribute__((aligned(16))) mrz_deep_rec {  // a helper-scanned lane's record on its way to the committer
+    int64_t occ_t, occ_off;      // granule 0
+    int64_t old_t, old_t2;       // 1
+    int64_t cp_scan, alt_old_t;  // 2
+    int alt_w, h, fe, w;         // 3
+    int h2, w2;                  // 4
+    unsigned short xw_seen;
+    unsigned char kind, kind2, nsame, flags, alt_kind, pad;
+    mrz_deep_rec_ent ent[MRZ_SMAX];  // 5 ...: the first nsame are written
+};
+static_assert(sizeof(mrz_deep_rec_ent) == 16 && sizeof(mrz_deep_rec) == 16 * MRZ_DEEP_REC_GRANULES, "records travel as 16-byte granules");
+
+struct __attribute__((aligned(16))) mrz_deep_stamp {  // ONE granule: written by one store, read by one load
+    unsigned long long job_seq;  // the batch these belong to
+    int nb, nscan;
+};
+
+struct mrz_deep_shared {  // device memory; everything before `q` is zeroed by the host before every launch
     // polled control words (agent scope), one 128-byte line
     unsigned long long seq;        // number of the batch posted last (0: none yet)
     unsigned long long quit;       // the launch is over
@@ -497,13 +556,18 @@ struct mrz_deep_shared {  // device memory, zeroed by the host before every laun
     unsigned long long xcc_plus1;  // the committer's XCC id + 1 (0: not yet posted)
     unsigned long long pad0[12];
     // the job of batch `seq`, one line
-    long long nb, nscan, better, tag_mask, clean_ptr, xw_n;
+    mrz_deep_stamp stamp;
+    long long better, tag_mask, clean_ptr, xw_n;
     long long pad1[10];
-    // lanes the helpers have finished for batch `seq`, its own line
+    // lanes the helpers have finished since the launch began, its own line
     unsigned long long done;
     unsigned long long pad2[15];
-    mrz_deep_recs R;  // q / t of every lane (committer), everything else of the helpers' lanes (helpers)
+    int64_t q[MRZ_DEEP_LANES], t[MRZ_DEEP_LANES];  // every lane's position and tag (committer)
+    mrz_deep_rec rec[MRZ_DEEP_LANES];              // the helpers' lanes' records (helpers)
 };
+static_assert(offsetof(mrz_deep_shared, stamp) % 128 == 0 && offsetof(mrz_deep_shared, done) % 128 == 0 &&
+                  offsetof(mrz_deep_shared, q) % 128 == 0 && offsetof(mrz_deep_shared, rec) % 16 == 0,
+              "the polled words, the job and the counter have lines of their own; granules are aligned");
 
 #ifdef __HIP_DEVICE_COMPILE__
 #define MRZ_DEEP_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
@@ -515,34 +579,156 @@ struct mrz_deep_shared {  // device memory, zeroed by the host before every laun
 #define MRZ_DEEP_XCC_ID() 0
 #endif
 
-// copies the scan record of lane i (everything but q / t) from `src` to `dst`; called by the lane's own thread
-__device__ __forceinline__ void mrz_deep_rec_copy(mrz_deep_recs *dst, const mrz_deep_recs *src, int i) {
-    dst->occ_t[i] = src->occ_t[i];
-    dst->occ_off[i] = src->occ_off[i];
-    dst->old_t[i] = src->old_t[i];
-    dst->old_t2[i] = src->old_t2[i];
-    dst->cp_scan[i] = src->cp_scan[i];
-    dst->alt_old_t[i] = src->alt_old_t[i];
-    dst->alt_w[i] = src->alt_w[i];
-    dst->alt_kind[i] = src->alt_kind[i];
-    dst->h[i] = src->h[i];
-    dst->fe[i] = src->fe[i];
-    dst->w[i] = src->w[i];
-    dst->h2[i] = src->h2[i];
-    dst->w2[i] = src->w2[i];
-    dst->xw_seen[i] = src->xw_seen[i];
-    dst->kind[i] = src->kind[i];
-    dst->kind2[i] = src->kind2[i];
-    dst->flags[i] = src->flags[i];
-    const int ns = src->nsame[i];
-    dst->nsame[i] = (unsigned char)ns;
-    for (int k = 0; k < ns; k++) {
-        dst->same_slot[i][k] = src->same_slot[i][k];
-        dst->same_off[i][k] = src->same_off[i][k];
-        dst->raw[i][k] = src->raw[i][k];
+// granule `g` of lane i's record, from the record arrays in LDS (little-endian: the layout of mrz_deep_rec).  Out of line
+// on purpose: inlined into the helper it shares registers with mrz_deep_scan's loop (spills there); the price is a call
+// per record and flat loads from LDS through the generic pointer, a dozen instructions beside a 10 us scan.
+__device__ static __attribute__((noinline)) uint4 mrz_deep_rec_granule(const mrz_deep_recs *R, int i, int g) {
+    if (g < 3) {
+        const int64_t a = g == 0 ? R->occ_t[i] : g == 1 ? R->old_t[i] : R->cp_scan[i];
+        const int64_t b = g == 0 ? R->occ_off[i] : g == 1 ? R->old_t2[i] : R->alt_old_t[i];
+        return make_uint4((uint32_t)(uint64_t)a, (uint32_t)((uint64_t)a >> 32), (uint32_t)(uint64_t)b, (uint32_t)((uint64_t)b >> 32));
+    }
+    if (g == 3) return make_uint4((uint32_t)R->alt_w[i], (uint32_t)R->h[i], (uint32_t)R->fe[i], (uint32_t)R->w[i]);
+    if (g == 4)
+        return make_uint4((uint32_t)R->h2[i], (uint32_t)R->w2[i],
+                          (uint32_t)R->xw_seen[i] | ((uint32_t)R->kind[i] << 16) | ((uint32_t)R->kind2[i] << 24),
+                          (uint32_t)R->nsame[i] | ((uint32_t)R->flags[i] << 8) | ((uint32_t)R->alt_kind[i] << 16));
+    const int k = g - MRZ_DEEP_REC_HDR;
+    const int64_t o = R->same_off[i][k];
+    return make_uint4((uint32_t)(uint64_t)o, (uint32_t)((uint64_t)o >> 32), (uint32_t)R->same_slot[i][k], (uint32_t)R->raw[i][k]);
+}
+
+// ... and back: granule `g` (`nsame` = the record's, from its granule 4) into the record arrays in LDS
+__device__ __forceinline__ void mrz_deep_rec_ungranule(mrz_deep_recs *R, int i, int g, uint4 v, int nsame) {
+    const int64_t a = (int64_t)(((uint64_t)v.y << 32) | v.x), b = (int64_t)(((uint64_t)v.w << 32) | v.z);
+    if (g == 0) {
+        R->occ_t[i] = a;
+        R->occ_off[i] = b;
+    } else if (g == 1) {
+        R->old_t[i] = a;
+        R->old_t2[i] = b;
+    } else if (g == 2) {
+        R->cp_scan[i] = a;
+        R->alt_old_t[i] = b;
+    } else if (g == 3) {
+        R->alt_w[i] = (int)v.x;
+        R->h[i] = (int)v.y;
+        R->fe[i] = (int)v.z;
+        R->w[i] = (int)v.w;
+    } else if (g == 4) {
+        R->h2[i] = (int)v.x;
+        R->w2[i] = (int)v.y;
+        R->xw_seen[i] = (unsigned short)(v.z & 0xffffu);
+        R->kind[i] = (unsigned char)((v.z >> 16) & 0xffu);
+        R->kind2[i] = (unsigned char)(v.z >> 24);
+        R->nsame[i] = (unsigned char)(v.w & 0xffu);
+        R->flags[i] = (unsigned char)((v.w >> 8) & 0xffu);
+        R->alt_kind[i] = (unsigned char)((v.w >> 16) & 0xffu);
+    } else if (g - MRZ_DEEP_REC_HDR < nsame) {
+        const int k = g - MRZ_DEEP_REC_HDR;
+        R->same_off[i][k] = a;
+        R->same_slot[i][k] = (int)v.z;
+        R->raw[i][k] = (unsigned short)(v.w & 0xffffu);
     }
 }
 
+// the records' granules in device memory: write-through (sc1) stores and sc1 loads to registers through a buffer
+// descriptor over G->rec (byte offsets; out-of-range accesses are dropped by the range check); plain ones in the fenced
+// form and in the emulator
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MRZ_DEEP_HANDOFF_FENCED)
+#define MRZ_DEEP_SC1 16  // the cache-policy bit of the buffer builtins' last argument
+typedef uint32_t mrz_v4u __attribute__((ext_vector_type(4)));
+struct mrz_deep_recmem {
+    __amdgpu_buffer_rsrc_t rsrc;
+};
+__device__ __forceinline__ mrz_deep_recmem mrz_deep_recmem_of(mrz_deep_shared *G) {
+    // (built from values the compiler can see are wave-uniform, also inside a function that is not inlined)
+    mrz_deep_recmem m;
+    m.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)mrz_uni64((int64_t)(uintptr_t)G->rec), 0, (int)sizeof(G->rec), 0x00020000);
+    return m;
+}
+__device__ __forceinline__ void mrz_deep_granule_store(const mrz_deep_recmem &m, unsigned off, uint4 v) {
+    mrz_v4u x = {v.x, v.y, v.z, v.w};
+    __builtin_amdgcn_raw_buffer_store_b128(x, m.rsrc, (int)off, 0, MRZ_DEEP_SC1);
+}
+// (`soff`: a wave-uniform part of the offset, kept out of the per-lane register.  A lane that does not `take` loads from
+// an offset far beyond the descriptor's range: the range check drops the access and gives zeros, and the loads of a trip
+// stand in a row with no branch -- and so no wait -- between them)
+__device__ __forceinline__ uint4 mrz_deep_granule_load(const mrz_deep_recmem &m, bool take, unsigned off, int soff) {
+    const mrz_v4u x = __builtin_amdgcn_raw_buffer_load_b128(m.rsrc, (int)(take ? off : 0x40000000u), soff, MRZ_DEEP_SC1);
+    return make_uint4(x[0], x[1], x[2], x[3]);
+}
+#else
+struct mrz_deep_recmem {
+    char *base;
+};
+__device__ __forceinline__ mrz_deep_recmem mrz_deep_recmem_of(mrz_deep_shared *G) {
+    mrz_deep_recmem m;
+    m.base = (char *)G->rec;
+    return m;
+}
+__device__ __forceinline__ void mrz_deep_granule_store(const mrz_deep_recmem &m, unsigned off, uint4 v) {
+    *(uint4 *)(m.base + off) = v;
+}
+__device__ __forceinline__ uint4 mrz_deep_granule_load(const mrz_deep_recmem &m, bool take, unsigned off, int soff) {
+    return take ? *(const uint4 *)(m.base + off + soff) : make_uint4(0, 0, 0, 0);
+}
+#endif
+
+// the wave that has scanned lane i sends its record: the header and the entries there are, ONE store instruction
+__device__ __forceinline__ void mrz_deep_rec_send(const mrz_deep_recmem &m, const mrz_deep_lds *S, int i, int lane) {
+    MRZ_WAVE_SYNC();  // (lane 0's and the probing lanes' LDS stores of mrz_deep_scan)
+    const int ng = MRZ_DEEP_REC_HDR + mrz_uni((int)S->R.nsame[i]);
+    if (lane < ng) mrz_deep_granule_store(m, (unsigned)(i * (int)sizeof(mrz_deep_rec) + lane * 16), mrz_deep_rec_granule(&S->R, i, lane));
+}
+
+// The committer fetches the helpers' lanes' records (lanes i < nb with i % nscan != 0) into S->R; all threads.  How many
+// entry granules a record has is not known before its header is there, and most have none or one: the header and the
+// FIRST entry granule of every record come in one trip, the further entries of the few records that have them in a
+// second one.  First trip: six threads per record, MRZ_DEEP_FETCH_PER records per load instruction of the workgroup;
+// a thread's j-th load is its first one's per-lane offset plus a wave-uniform constant, so the loads need one address
+// register between them and are issued back to back (one offset per load, each hoisted out of the batch loop and
+// spilled, made every load wait for a reload from scratch, and with it for the load before).  (The first entry granule
+// of a record without entries holds what an earlier batch left there: it lands behind nsame in S->R, where nothing reads.)
+#define MRZ_DEEP_REC_FIRST (MRZ_DEEP_REC_HDR + 1)
+#define MRZ_DEEP_FETCH_PER (MRZ_DEEP_THREADS / MRZ_DEEP_REC_FIRST)
+__device__ __forceinline__ void mrz_deep_recs_fetch(mrz_deep_shared *G, mrz_deep_lds *S, int nb, int nscan, int tid) {
+    const mrz_deep_recmem m = mrz_deep_recmem_of(G);
+    constexpr int NLD = (MRZ_DEEP_LANES + MRZ_DEEP_FETCH_PER - 1) / MRZ_DEEP_FETCH_PER;
+    constexpr int CH = 5;  // entry granules per trip of the second step
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+v"(tid));  // (what follows is worked out here, from one register, not kept across the batch loop)
+#endif
+    const int i0 = tid / MRZ_DEEP_REC_FIRST, g = tid - i0 * MRZ_DEEP_REC_FIRST;
+    const unsigned off0 = (unsigned)(i0 * (int)sizeof(mrz_deep_rec) + g * 16);
+    bool take[NLD];
+#pragma unroll
+    for (int j = 0; j < NLD; j++) {
+        const int i = i0 + j * MRZ_DEEP_FETCH_PER;
+        take[j] = i0 < MRZ_DEEP_FETCH_PER && i < nb && i % nscan != 0;
+    }
+    uint4 v[NLD];
+#pragma unroll
+    for (int j = 0; j < NLD; j++) {
+        v[j] = mrz_deep_granule_load(m, take[j], off0, j * MRZ_DEEP_FETCH_PER * (int)sizeof(mrz_deep_rec));
+    }
+#pragma unroll
+    for (int j = 0; j < NLD; j++)
+        if (take[j]) mrz_deep_rec_ungranule(&S->R, i0 + j * MRZ_DEEP_FETCH_PER, g, v[j], MRZ_SMAX);
+    __syncthreads();  // (nsame of every record is in LDS)
+    const int ns = (tid < nb && tid % nscan != 0) ? (int)S->R.nsame[tid] : 0;
+    for (int k0 = 1; __ballot(k0 < ns) != 0; k0 += CH) {
+        const unsigned offe = (unsigned)(tid * (int)sizeof(mrz_deep_rec) + (MRZ_DEEP_REC_HDR + k0) * 16);
+        uint4 e[CH];
+#pragma unroll
+        for (int c = 0; c < CH; c++) {
+            e[c] = mrz_deep_granule_load(m, k0 + c < ns, offe, c * 16);
+        }
+#pragma unroll
+        for (int c = 0; c < CH; c++)
+            if (k0 + c < ns) mrz_deep_rec_ungranule(&S->R, tid, MRZ_DEEP_REC_HDR + k0 + c, e[c], ns);
+    }
+}
 
 // a scan helper workgroup: see above
 __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, mrz_deep_shared *G, int tid, int lane, int wave) {
@@ -562,7 +748,13 @@ __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, m
     const int ticket = mrz_uni(S->ctl[0]);
     if (ticket < 0 || ticket >= MRZ_DEEP_SCANNERS) return;
     const int me = ticket + 1;  // my share: lanes i with i % nscan == me
+    const mrz_deep_recmem recmem = mrz_deep_recmem_of(G);
     unsigned long long seen = 0;
+    int retries = 0;  // looks in a row at a job line whose stamp was not the number polled (wave-uniform)
+#ifdef MRZ_SEQ_PROFILE
+    int64_t hprof[4] = {0, 0, 0, 0};  // (ticket 0's thread 0 reports: MRZ_ST_DH_T_ACQ ...)
+#endif
+    DPROF_T0();
     while (true) {
         if (tid == 0) {
             long long spins = 0;
@@ -570,43 +762,72 @@ __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, m
             int v = 1;
             while (true) {
                 sq = __hip_atomic_load(&G->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (sq != seen) break;
+                if (sq != seen && retries == 0) break;
                 if (__hip_atomic_load(&G->quit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || spins++ > MRZ_HELPER_SPIN_LIMIT) {
                     v = 0;
                     break;
                 }
+                if (sq != seen) break;  // (a look again after a stamp that did not match: behind the look at `quit`)
                 __builtin_amdgcn_s_sleep(2);
             }
+            DPROF_T0R();
             MRZ_DEEP_ACQUIRE();  // nothing of the job, nor of the table, is served from this CU's L1 from before
+            MRZ_DEEP_WAIT();     // (the invalidate has completed before the barrier lets the other waves load)
             S->ctl[1] = v;
             S->lead.p = (int64_t)sq;
         }
         __syncthreads();
-        if (!mrz_uni(S->ctl[1])) return;
-        seen = (unsigned long long)mrz_uni64(S->lead.p);
-        const int nb = (int)G->nb, nscan = (int)G->nscan, xw_n = (int)G->xw_n;
+        if (!mrz_uni(S->ctl[1])) break;
+        DPROF_ADD(hprof[0]);
+        const unsigned long long sq = (unsigned long long)mrz_uni64(S->lead.p);
+        const uint4 sv = *(const uint4 *)&G->stamp;  // {job_seq, nb, nscan}: one load
+        const unsigned long long job_seq = (unsigned long long)mrz_uni64((int64_t)(((unsigned long long)sv.y << 32) | sv.x));
+        const int nb = mrz_uni((int)sv.z), nscan = mrz_uni((int)sv.w);
+        const int xw_n = (int)G->xw_n;
         const int64_t better = G->better, tag_mask = G->tag_mask, clean_ptr = G->clean_ptr;
+        if (job_seq != sq) {  // the line belongs to another batch than the one polled (a late check-in): not mine, look again
+            if (++retries > MRZ_DEEP_STAMP_RETRIES) break;  // (bounded like every wait here; the post of a batch takes microseconds)
+            __syncthreads();  // (thread 0 writes ctl / lead again)
+            continue;
+        }
+        retries = 0;
+        seen = sq;
         int mine_n = 0;
         if (me < nscan) {
             for (int i = me + tid * nscan; i < nb; i += nscan * MRZ_DEEP_THREADS) {
-                S->R.q[i] = G->R.q[i];
-                S->R.t[i] = G->R.t[i];
+                S->R.q[i] = G->q[i];
+                S->R.t[i] = G->t[i];
             }
             __syncthreads();
+            DPROF_ADD(hprof[1]);
             int k = 0;
             for (int i = me; i < nb; i += nscan, k++)
-                if (k % MRZ_DEEP_WAVES == wave) mrz_deep_scan(C, S, i, better, tag_mask, clean_ptr, xw_n, lane);
+                if (k % MRZ_DEEP_WAVES == wave) {
+                    mrz_deep_scan(C, S, i, better, tag_mask, clean_ptr, xw_n, lane);
+                    mrz_deep_rec_send(recmem, S, i, lane);
+                }
             mine_n = k;
-            __syncthreads();
-            for (int i = me + tid * nscan; i < nb; i += nscan * MRZ_DEEP_THREADS) mrz_deep_rec_copy(&G->R, &S->R, i);
-            MRZ_DEEP_WAIT();
+            MRZ_DEEP_WAIT();  // every storing wave: its granules have left
+#ifdef MRZ_SEQ_PROFILE
+            __syncthreads();  // (the barrier below, taken here for the timer)
+            DPROF_ADD(hprof[2]);
+#endif
         }
         __syncthreads();
         if (tid == 0 && mine_n) {
+#ifdef MRZ_DEEP_HANDOFF_FENCED
             MRZ_DEEP_RELEASE();
-            __hip_atomic_fetch_add(&G->done, (unsigned long long)mine_n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            MRZ_DEEP_WAIT();  // (the fence's own wait, where the compiler cannot drop it)
+#endif
+            __hip_atomic_fetch_add(&G->done, (unsigned long long)mine_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            DPROF_ADD(hprof[3]);
         }
     }
+#ifdef MRZ_SEQ_PROFILE
+    // (the committer leaves these four slots alone; one launch at a time runs on a context's state)
+    if (tid == 0 && ticket == 0)
+        for (int k = 0; k < 4; k++) C.st->prof[MRZ_ST_DH_T_ACQ + k] += hprof[k];
+#endif
 }
 
 // (out of line: the cooperative path is large and rare -- inlined, twice, it cost the scan loop 120 spilled registers)
@@ -791,6 +1012,7 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
     }
     if (tid == 0 && G) __hip_atomic_store(&G->xcc_plus1, (unsigned long long)MRZ_DEEP_XCC_ID() + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned long long batch_seq = 0;
+    unsigned long long done_target = 0;  // helper lanes dealt out so far: what `done` reaches when the batch's are back
     const int64_t lim = (C.end < K.seg_end - 1) ? C.end : K.seg_end - 1;  // last candidate position of this launch
     const int smask = (int)C.slot_mask;
     const int max_chain = (int)C.max_chain;
@@ -875,6 +1097,7 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
         ST_ADD(MRZ_ST_D_LANES, nb);
         PROF_ADD(MRZ_ST_D_T_FORM);
         // ---- SCAN --------------------------------------------------------------------------------------------------
+        DPROF_T0();
         if (!loose) {
             // how many workgroups scan this batch: the helpers that have checked in take lanes i with i % nscan != 0
             int nscan = 1;
@@ -886,27 +1109,29 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
             }
             int helper_lanes = 0;
             if (nscan > 1) {
+                batch_seq++;
                 if (tid < nb) {
-                    G->R.q[tid] = S->R.q[tid];
-                    G->R.t[tid] = S->R.t[tid];
+                    G->q[tid] = S->R.q[tid];
+                    G->t[tid] = S->R.t[tid];
                 }
                 if (tid == 0) {
-                    G->nb = nb;
-                    G->nscan = nscan;
+                    // {job_seq, nb, nscan}: ONE 16-byte store (the stamp and what it vouches for do not come apart)
+                    *(uint4 *)&G->stamp = make_uint4((uint32_t)batch_seq, (uint32_t)(batch_seq >> 32), (uint32_t)nb, (uint32_t)nscan);
                     G->better = better;
                     G->tag_mask = L.tag_mask;
                     G->clean_ptr = L.clean_ptr;
                     G->xw_n = 0;
-                    __hip_atomic_store(&G->done, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 MRZ_DEEP_WAIT();  // every thread's job stores (and, before them, the table stores of the last commit)
                 __syncthreads();
-                batch_seq++;
                 if (tid == 0) {
-                    MRZ_DEEP_RELEASE();
-                    __hip_atomic_store(&G->seq, batch_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                    MRZ_DEEP_RELEASE();  // ONE write-back: the table stores of the last commit and the job
+                    MRZ_DEEP_WAIT();     // (the fence's own wait, where the compiler cannot drop it)
+                    __hip_atomic_store(&G->seq, batch_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 helper_lanes = nb - (nb + nscan - 1) / nscan;
+                done_target += (unsigned long long)helper_lanes;
+                DPROF_ADD(stat[MRZ_ST_D_T_POST]);
             }
             {
                 int k = 0;
@@ -914,20 +1139,28 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
                     if (k % MRZ_DEEP_WAVES == wave) mrz_deep_scan(C, S, i, better, L.tag_mask, L.clean_ptr, 0, lane);
             }
             if (nscan > 1) {
+                DPROF_ADD(stat[MRZ_ST_D_T_OWN]);
                 if (tid == 0) {
                     long long spins = 0;
-                    while (__hip_atomic_load(&G->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (unsigned long long)helper_lanes &&
-                           spins++ < (1ll << 26))
+                    while (__hip_atomic_load(&G->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < done_target && spins++ < (1ll << 26))
                         __builtin_amdgcn_s_sleep(1);
                     S->ctl[6] = spins < (1ll << 26) ? 1 : 0;
+#ifdef MRZ_DEEP_HANDOFF_FENCED
                     MRZ_DEEP_ACQUIRE();  // the helpers' records are not served from lines this CU's L1 held before
+                    MRZ_DEEP_WAIT();     // (the invalidate has completed before the barrier lets the other waves load)
+#endif
                 }
-                __syncthreads();
+                __syncthreads();  // (the polling wave joins it after its poll has matched: the other waves load behind it)
+                DPROF_ADD(stat[MRZ_ST_D_T_WAIT]);
                 if (!mrz_uni(S->ctl[6])) {  // cannot happen: a helper that has checked in answers
                     if (tid == 0) C.st->error = 7;
                     ok = false;
-                } else if (tid < nb && tid % nscan != 0)
-                    mrz_deep_rec_copy(&S->R, &G->R, tid);
+                } else
+                    mrz_deep_recs_fetch(G, S, nb, nscan, tid);
+#ifdef MRZ_SEQ_PROFILE
+                __syncthreads();  // (the records are in: the barrier below, taken here for the timer)
+                DPROF_ADD(stat[MRZ_ST_D_T_COPYIN]);
+#endif
             }
         }
         __syncthreads();
@@ -1433,7 +1666,8 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
         st->hint_events = L.n_events - hint_ev0;
         st->hint_matched = L.mbytes;
 #ifdef MRZ_SEQ_STATS
-        for (int k = 0; k < MRZ_ST_N; k++) st->prof[k] += stat[k];
+        for (int k = 0; k < MRZ_ST_N; k++)
+            if (k < MRZ_ST_DH_T_ACQ || k > MRZ_ST_DH_T_OUT) st->prof[k] += stat[k];  // (those: the scan helper with ticket 0)
 #endif
     }
 }
@@ -1479,7 +1713,7 @@ extern "C" hipError_t mrz_launch_sequencer_deep(hipStream_t stream, const uint8_
     while (scanners > 0 && grid < (unsigned)(scanners + 2)) scanners--;  // (blocks there are)
 #endif
     if (deep_shared) {
-        hipError_t e = hipMemsetAsync(deep_shared, 0, offsetof(mrz_deep_shared, R), stream);
+        hipError_t e = hipMemsetAsync(deep_shared, 0, offsetof(mrz_deep_shared, q), stream);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(mrz_seq_deep_kernel, dim3(grid), dim3(MRZ_DEEP_THREADS), 0, stream, a, (mrz_deep_shared *)deep_shared,
