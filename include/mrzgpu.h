@@ -307,6 +307,20 @@ int mrz_lz4_compress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t 
 int mrz_lz4_decompress_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *c_lens, int count, int where,
                              void *const *outs, const int64_t *u_lens, int out_where, int32_t *status);
 
+/* The first wants[i] bytes of what block i decodes to, 0 <= wants[i] <= u_lens[i] (anything else: MRZ_E_ARG, as are
+ * the cases above); outs[i] needs room for wants[i] bytes only.  One wave per block, one launch per call.  The walk
+ * and its rules are those of mrz_lz4_decompress_batch, applied to the block's real c_lens[i] and u_lens[i], offset 0
+ * rejected.  The copy (a literal run or a match) with which the output reaches wants[i] is validated as the full
+ * decoder validates it before it copies -- and a closing literal run must end at u_lens[i] --, then cut: exactly
+ * wants[i] bytes are written, nothing at or beyond outs[i] + wants[i], nothing outside bufs[i][0, c_lens[i]) is read.
+ * THE CONTRACT: a reject that the full walk meets only behind that copy is NOT seen (status 0, and the bytes are
+ * what every sequence up to there says): the same trade range decode makes for the CRC.  A block accepted at one
+ * `want` is accepted at every smaller one, with the same bytes.  wants[i] == u_lens[i] is the full decoder, bit for
+ * bit in status and bytes; wants[i] == 0 < u_lens[i] reads and writes nothing and gives status 0. */
+int mrz_lz4_decompress_prefix_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *c_lens, int count, int where,
+                                    void *const *outs, const int64_t *u_lens, const int64_t *wants, int out_where,
+                                    int32_t *status);
+
 /* ---- BLAKE2b (co-resident checksum kernel) ------------------------------ */
 
 /* Streaming triple mirroring common/blake2b.h:47-49

@@ -121,8 +121,8 @@ int mrz_rzip_pipeline(const mrz_control *control, const void *in, int64_t n, mrz
  * *out is malloc'd by the library (mrz_free).  Record decoding runs on the GPU (mrz_runzip_chunk). */
 int mrz_runzip_buffer(int device, const void *mrz, int64_t n, void **out, int64_t *out_len);
 
-/* CTYPE_NONE blocks only: range decode over LZ4 blocks is out of scope, an archive that holds one gets
- * MRZ_E_UNSUPPORTED here (mrz_runzip_buffer decodes it whole).
+/* CTYPE_NONE blocks only: an archive that holds an LZ4 block gets MRZ_E_UNSUPPORTED here (mrz_runzip_buffer decodes it
+ * whole).  Ranges of such an archive: mrz_runzip_buffer_range_ex below.
  * Bytes [first, first + count) of the file a -n archive decodes to, written to out_host; *file_len (may be NULL) is the
  * file's length: the header's where it carries one, otherwise the chunks are walked to the end.  Same header rules and
  * refusals as mrz_runzip_buffer (MRZ_E_UNSUPPORTED, MRZ_E_CORRUPT); first < 0, count < 0 or a range beyond the file
@@ -134,6 +134,30 @@ int mrz_runzip_buffer(int device, const void *mrz, int64_t n, void **out, int64_
  * The MD5 / per-chunk CRC is NOT checked: either needs every byte.  Use mrz_runzip_buffer for a verified decode. */
 int mrz_runzip_buffer_range(int device, const void *mrz, int64_t n, int64_t first, int64_t count, void *out_host,
                             int64_t *file_len);
+
+/* The same range over an archive whose blocks are CTYPE_NONE or CTYPE_LZ4, mixed freely (block acceptance and its
+ * refusals: mrz_runzip_buffer; header rules, *file_len, MRZ_E_ARG / MRZ_E_CORRUPT cases, the early stop behind a header
+ * that carries the size and NO MD5 / CRC check: mrz_runzip_buffer_range).  `out` is host or device memory per
+ * out_where; nothing beyond `count` bytes is written.  `info` may be NULL.
+ * Per chunk: a stream 0 without an LZ4 block is gathered and walked on the host as above; one with an LZ4 block is put
+ * together on the device, its LZ4 blocks decoded WHOLE (the parse needs every record), and the chunk's length comes
+ * from that parse.  Chunks outside the range do no more.  Inside the range the origins stay on the device
+ * (mrz_runzip_origins), one kernel finds per stream-1 block the lowest and highest offset an origin asks of it, and
+ * only that table (8 bytes a block) comes back.  A touched LZ4 block has its payload uploaded and its first
+ * `highest + 1` bytes decoded (mrz_lz4_decompress_prefix_batch, all touched blocks of the chunk in one launch); of a
+ * touched CTYPE_NONE block bytes [lowest, highest] are uploaded; a second kernel gathers the range from those pieces.
+ * A prefix the decoder rejects is MRZ_E_CORRUPT; a defect behind the highest origin of a block, or in a block that
+ * holds no origin, is not seen.  Stream 1 never exists whole anywhere: device memory per chunk is bounded by stream 0
+ * + the touched payloads + the prefixes + 9 bytes per range byte (+ 24 bytes per block). */
+typedef struct {
+    int64_t chunks_in_range, total_hops, max_hops;      /* as mrz_range_info, summed / maxed over the chunks */
+    int64_t s0_lz4_bytes;        /* bytes of stream 0 that were LZ4-decoded (always whole blocks) */
+    int64_t s1_blocks_touched;   /* stream-1 blocks holding at least one origin */
+    int64_t s1_lz4_bytes;        /* sum of `want` over the touched LZ4 blocks of stream 1 */
+    int64_t s1_bytes_uploaded;   /* payload bytes of stream 1 sent to the device */
+} mrz_archive_range_info;
+int mrz_runzip_buffer_range_ex(int device, const void *mrz, int64_t n, int64_t first, int64_t count, void *out,
+                               int out_where, int64_t *file_len, mrz_archive_range_info *info);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ from .binding import (  # noqa: E402,F401
     rzip_fd,
     runzip_buffer,
     runzip_buffer_range,
+    runzip_buffer_range_ex,
     rzip_pipeline,
     MEM_HOST,
     MEM_DEVICE,
@@ -39,5 +40,5 @@ from .binding import (  # noqa: E402,F401
 
 __all__ = [
     "MrzError", "RzipContext", "WindowPart", "WindowMap", "window_granularity", "ChunkResult", "Stats", "Timings", "Control", "lib_path", "load_library",
-    "chunk_bytes", "rzip_buffer", "rzip_buffer_lz4", "rzip_stream_buffer", "rzip_fd", "runzip_buffer", "runzip_buffer_range", "rzip_pipeline", "MEM_HOST", "MEM_DEVICE",
+    "chunk_bytes", "rzip_buffer", "rzip_buffer_lz4", "rzip_stream_buffer", "rzip_fd", "runzip_buffer", "runzip_buffer_range", "runzip_buffer_range_ex", "rzip_pipeline", "MEM_HOST", "MEM_DEVICE",
 ]

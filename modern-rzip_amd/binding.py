@@ -59,6 +59,15 @@ class RangeInfo(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ArchiveRangeInfo(ctypes.Structure):
+    """mrz_archive_range_info (include/mrzgpu_host.h)."""
+    _fields_ = [(n, ctypes.c_int64) for n in ("chunks_in_range", "total_hops", "max_hops", "s0_lz4_bytes",
+                                              "s1_blocks_touched", "s1_lz4_bytes", "s1_bytes_uploaded")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Control(ctypes.Structure):
     """The rzip_control fields rzip_fd reads for `mrzip -n` (include/mrzgpu_host.h)."""
     _fields_ = [("rzip_compression_level", ctypes.c_int), ("compression_level", ctypes.c_int),
@@ -171,6 +180,10 @@ def load_library(path=None):
         lib.mrz_lz4_decompress_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci,
                                                  ctypes.POINTER(vp), ctypes.POINTER(i64), ci,
                                                  ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "mrz_lz4_decompress_prefix_batch"):
+        lib.mrz_lz4_decompress_prefix_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci,
+                                                        ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), ci,
+                                                        ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "mrz_rzip_buffer_lz4"):
         lib.mrz_rzip_buffer_lz4.argtypes = [ctypes.POINTER(Control), ci, vp, i64, ctypes.POINTER(vp),
                                             ctypes.POINTER(i64), ctypes.POINTER(Stats), vp]
@@ -194,6 +207,9 @@ def load_library(path=None):
         lib.mrz_runzip_buffer.argtypes = [ci, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
     if hasattr(lib, "mrz_runzip_buffer_range"):
         lib.mrz_runzip_buffer_range.argtypes = [ci, vp, i64, i64, i64, vp, ctypes.POINTER(i64)]
+    if hasattr(lib, "mrz_runzip_buffer_range_ex"):
+        lib.mrz_runzip_buffer_range_ex.argtypes = [ci, vp, i64, i64, i64, vp, ci, ctypes.POINTER(i64),
+                                                   ctypes.POINTER(ArchiveRangeInfo)]
     if hasattr(lib, "mrz_rzip_pipeline"):
         lib.mrz_rzip_pipeline.argtypes = [ctypes.POINTER(Control), vp, i64, BLOCK_FN, vp, ctypes.POINTER(Stats), vp]
     if hasattr(lib, "mrz_rzip_buffer"):
@@ -567,6 +583,26 @@ class RzipContext:
             return None, list(st)
         return [None if s else o.raw[:int(u)] for o, u, s in zip(outs, u_lens, st)], list(st)
 
+    def lz4_decompress_prefix_batch(self, blocks, u_lens, wants, outs=None):
+        """mrz_lz4_decompress_prefix_batch: the first wants[i] bytes of what block i decodes to (its full length is
+        u_lens[i]).  Returns (payloads, statuses) as lz4_decompress; a reject that lies behind the cut is not seen.
+        With outs (writable buffers of at least wants[i] bytes) the bytes go there and the first item is None."""
+        if not hasattr(self.lib, "mrz_lz4_decompress_prefix_batch"):
+            raise MrzError("this libmrzgpu has no mrz_lz4_decompress_prefix_batch: rebuild it")
+        blocks = list(blocks)
+        if not blocks:
+            return [], []
+        if len(u_lens) != len(blocks):
+            raise MrzError("lz4: one size (and one output) per block")
+        prep, oprep, outs, own, ip, il, op, wl = self._lz4_io(blocks, list(wants), outs)
+        ul = (ctypes.c_int64 * len(prep))(*[int(u) for u in u_lens])
+        st = (ctypes.c_int32 * len(prep))()
+        _check(self.lib, self.lib.mrz_lz4_decompress_prefix_batch(self.ctx, ip, il, len(prep), prep[0][2], op, ul, wl,
+                                                                  oprep[0][2], st), self.ctx)
+        if not own:
+            return None, list(st)
+        return [None if s else o.raw[:int(w)] for o, w, s in zip(outs, wants, st)], list(st)
+
     # ---- rs-mrzip encoder (rs-mrzip/rs-mrzip.c:119-158) ----
     def rs_encode(self, data):
         ptr, n, where, keep = _as_ptr(data)
@@ -847,6 +883,36 @@ def runzip_buffer_range(mrz, first, count, device=0, lib=None):
         e.file_len = file_len.value if file_len.value >= 0 else None
         raise
     return buf.raw[:max(0, count)], file_len.value
+
+
+def runzip_buffer_range_ex(mrz, first, count, out=None, device=0, lib=None):
+    """mrz_runzip_buffer_range_ex: runzip_buffer_range over an archive whose blocks may be LZ4 (`mrzip -l`): only the
+    stream-1 blocks that hold a byte of the range are decoded, each as far as its highest byte asked for.  Returns
+    (bytes or None, file_len, info dict: mrz_archive_range_info); with `out` = a cuda tensor or a (device pointer, nbytes)
+    pair the bytes stay on the device.  A refusal raises MrzError with .rc and .file_len (None where the archive was
+    refused before its length was known)."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_runzip_buffer_range_ex"):
+        raise MrzError("this libmrzgpu has no mrz_runzip_buffer_range_ex: rebuild it")
+    ptr, n, where, keep = _as_ptr(mrz)
+    if where != MEM_HOST:
+        raise MrzError("runzip_buffer_range_ex takes the archive in host memory")
+    if out is None:
+        buf = ctypes.create_string_buffer(max(1, count))
+        po, wo = ctypes.cast(buf, ctypes.c_void_p), MEM_HOST
+    else:
+        po, no, wo, ko = _as_ptr(out)
+        if no < count:
+            raise MrzError("runzip_buffer_range_ex: the output buffer is smaller than the range asked for")
+    file_len = ctypes.c_int64(-1)
+    info = ArchiveRangeInfo()
+    try:
+        _check(lib, lib.mrz_runzip_buffer_range_ex(device, ptr, n, first, count, po, wo, ctypes.byref(file_len),
+                                                   ctypes.byref(info)))
+    except MrzError as e:
+        e.file_len = file_len.value if file_len.value >= 0 else None
+        raise
+    return (buf.raw[:max(0, count)] if out is None else None), file_len.value, info.as_dict()
 
 
 def rzip_pipeline(data, on_block, level=7, window=0, unlimited=False, ramsize=60 << 30, device=0, lib=None,

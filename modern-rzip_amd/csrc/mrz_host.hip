@@ -974,6 +974,7 @@ int64_t peek_le(const uint8_t *p, int nbytes) {
 // only CTYPE_NONE (3) blocks.  This is the walk of mrz_runzip_buffer_range, which gathers bytes straight from the
 // archive's blocks: range decode over LZ4 blocks is out of scope, such an archive gets MRZ_E_UNSUPPORTED there
 // (mrz_runzip_buffer reads it: list_stream below).
+// Ranges of an archive with LZ4 blocks: mrz_runzip_buffer_range_ex, at the end of this file.
 template <class F>
 int walk_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, F &&block, int64_t *end_max) {
     int64_t at = head_at;
@@ -1380,4 +1381,251 @@ extern "C" int mrz_runzip_buffer_range(int device, const void *mrz_v, int64_t n,
     } catch (const std::length_error &) {
         return MRZ_E_CORRUPT;
     }
+}
+
+// ---- ... and of a -l archive: stream 1 stays in its blocks, the touched ones are decoded as far as they are needed -----
+namespace {
+
+struct DeviceBuf {
+    uint8_t *p = nullptr;
+    ~DeviceBuf() {
+        if (p) hipFree(p);
+    }
+};
+
+struct CtxGuard {
+    mrz_ctx *ctx = nullptr;
+    ~CtxGuard() {
+        if (ctx) mrz_close(ctx);
+    }
+};
+
+// One entry of a chunk's stream-1 table: a block, or a piece of at most kLz4MaxInput bytes of a longer CTYPE_NONE
+// block, so that offsets inside an entry fit the 32 bits of mrz_uz_span.
+struct S1Piece {
+    size_t block;  // index into the chunk's stream-1 blocks
+    int64_t at;    // where the piece begins in its block
+};
+
+void s1_table(const std::vector<ArcBlock> &s1, std::vector<int64_t> &starts, std::vector<S1Piece> &pieces) {
+    int64_t at = 0;
+    for (size_t k = 0; k < s1.size(); k++) {
+        int64_t off = 0;
+        do {
+            starts.push_back(at + off);
+            pieces.push_back(S1Piece{ k, off });
+            off += kLz4MaxInput;
+        } while (off < s1[k].u_len);
+        at += s1[k].u_len;
+    }
+}
+
+// Bytes [lo, lo + cnt) of one chunk into d_out (device memory): origins, spans, the touched blocks' prefixes, gather.
+int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, int where0, const std::vector<ArcBlock> &s1,
+                       int64_t s1_len, int cb, int64_t lo, int64_t cnt, uint8_t *d_out, mrz_archive_range_info &acc) {
+    std::vector<int64_t> starts;
+    std::vector<S1Piece> pieces;
+    s1_table(s1, starts, pieces);
+    const int64_t nt = (int64_t)starts.size();
+    auto al = [](int64_t v) { return (v + 255) & ~255ll; };
+    const int64_t o_starts = al(cnt * 8), o_span = o_starts + al(nt * 8), o_base = o_span + al(nt * 8);
+    DeviceBuf tab;
+    if (hipMalloc((void **)&tab.p, (size_t)(o_base + al(nt * 8))) != hipSuccess) return MRZ_E_NOMEM;
+    int64_t *d_org = (int64_t *)tab.p, *d_starts = (int64_t *)(tab.p + o_starts), *d_base = (int64_t *)(tab.p + o_base);
+    mrz_uz_span *d_span = (mrz_uz_span *)(tab.p + o_span);
+
+    mrz_range_info ri;
+    int rc = mrz_runzip_origins(ctx, s0, s0_len, s1_len, where0, cb, lo, cnt, d_org, MRZ_MEM_DEVICE, &ri);
+    if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // the device's reading of the records differs from the length walk's
+    if (rc) return rc;
+    acc.chunks_in_range++;
+    acc.total_hops += ri.total_hops;
+    if (ri.max_hops > acc.max_hops) acc.max_hops = ri.max_hops;
+
+    std::vector<mrz_uz_span> span((size_t)nt, mrz_uz_span{ 0xffffffffu, 0u });
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d_starts, starts.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_span, span.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, mrz_launch_block_span(s, cus, d_org, cnt, d_starts, nt, d_span));
+    HIPCHK(ctx, hipMemcpyAsync(span.data(), d_span, (size_t)nt * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+
+    // what the touched entries need: LZ4 payloads in front, then per entry the bytes from its lowest offset on
+    int64_t packed = 0, staged = 0;
+    for (int64_t t = 0; t < nt; t++) {
+        if (span[(size_t)t].lo > span[(size_t)t].hi) continue;
+        const ArcBlock &b = s1[pieces[(size_t)t].block];
+        const int64_t hi = span[(size_t)t].hi, low = span[(size_t)t].lo;
+        if (pieces[(size_t)t].at + hi >= b.u_len) return MRZ_E_STATE;  // (an origin lies below s1_len: cannot happen)
+        if (b.ctype == kCtypeLz4) {
+            packed += (b.c_len + 31) & ~15ll;
+            staged += (hi + 1 + 31) & ~15ll;
+        } else
+            staged += (hi - low + 1 + 31) & ~15ll;
+    }
+    DeviceBuf stage;
+    if (hipMalloc((void **)&stage.p, (size_t)(packed + staged + 64)) != hipSuccess) return MRZ_E_NOMEM;
+    std::vector<int64_t> base((size_t)nt, 0);
+    std::vector<const void *> src;
+    std::vector<void *> dst;
+    std::vector<int64_t> c_lens, u_lens, wants;
+    int64_t pk = 0, st = packed;
+    size_t last_block = (size_t)-1;
+    for (int64_t t = 0; t < nt; t++) {
+        if (span[(size_t)t].lo > span[(size_t)t].hi) continue;
+        const S1Piece &pc = pieces[(size_t)t];
+        const ArcBlock &b = s1[pc.block];
+        const int64_t hi = span[(size_t)t].hi, low = span[(size_t)t].lo;
+        if (pc.block != last_block) acc.s1_blocks_touched++;
+        last_block = pc.block;
+        if (b.ctype == kCtypeLz4) {  // the prefix [0, hi]: a decode cannot begin anywhere else
+            if (b.c_len) HIPCHK(ctx, hipMemcpyAsync(stage.p + pk, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, s));
+            src.push_back(stage.p + pk);
+            dst.push_back(stage.p + st);
+            c_lens.push_back(b.c_len);
+            u_lens.push_back(b.u_len);
+            wants.push_back(hi + 1);
+            base[(size_t)t] = st + low;
+            pk += (b.c_len + 31) & ~15ll;
+            st += (hi + 1 + 31) & ~15ll;
+            acc.s1_lz4_bytes += hi + 1;
+            acc.s1_bytes_uploaded += b.c_len;
+        } else {  // bytes [low, hi] of the piece
+            HIPCHK(ctx, hipMemcpyAsync(stage.p + st, b.p + pc.at + low, (size_t)(hi - low + 1), hipMemcpyHostToDevice, s));
+            base[(size_t)t] = st;
+            st += (hi - low + 1 + 31) & ~15ll;
+            acc.s1_bytes_uploaded += hi - low + 1;
+        }
+    }
+    if (src.size() > 0x7fffffffu) return MRZ_E_UNSUPPORTED;
+    HIPCHK(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (!src.empty()) {
+        std::vector<int32_t> status(src.size());
+        rc = mrz_lz4_decompress_prefix_batch(ctx, src.data(), c_lens.data(), (int)src.size(), MRZ_MEM_DEVICE, dst.data(),
+                                             u_lens.data(), wants.data(), MRZ_MEM_DEVICE, status.data());
+        if (rc) return rc;
+        for (int32_t v : status)
+            if (v) return MRZ_E_CORRUPT;
+    }
+    HIPCHK(ctx, mrz_launch_block_gather(s, cus, d_org, cnt, d_starts, nt, d_span, d_base, stage.p, d_out));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return MRZ_OK;
+}
+
+}  // namespace
+
+static int runzip_buffer_range_ex_impl(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out,
+                                       int out_where, int64_t *file_len, mrz_archive_range_info &acc) {
+    if (!mrz_v || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE)) return MRZ_E_ARG;
+    const uint8_t *mrz = (const uint8_t *)mrz_v;
+    int64_t expected = 0;
+    int hash_code = 0;
+    int rc = read_archive_header(mrz, n, &expected, &hash_code);
+    if (rc) return rc;
+    const bool size_known = expected > 0;
+    if (size_known) {
+        if (file_len) *file_len = expected;
+        if (first < 0 || count < 0 || first > expected || count > expected - first) return MRZ_E_ARG;
+        if (!count) return MRZ_OK;
+        if (!out) return MRZ_E_ARG;
+    }
+    // without a size the file's length is still owed to a caller whose range is wrong: the walk goes on, the work does not
+    const bool bad_range = first < 0 || count < 0 || count > INT64_MAX - first || (count > 0 && !out);
+    CtxGuard g;
+    int cus = 0;
+    auto open_ctx = [&]() {  // on first need: an archive may be walked without any device work
+        if (g.ctx) return (int)MRZ_OK;
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        return mrz_open(&g.ctx, device, 7, 0);
+    };
+    DeviceBuf scratch;  // the range, when `out` is host memory
+    uint8_t *d_out = out_where == MRZ_MEM_DEVICE ? (uint8_t *)out : nullptr;
+    int64_t at = 20 + mrz[19], total = 0;
+    std::vector<uint8_t> s0;
+    for (;;) {
+        if (at + 2 > n) return MRZ_E_CORRUPT;
+        const int cb = mrz[at], eof = mrz[at + 1];
+        if (cb < 1 || cb > 8 || at + 2 + cb > n) return MRZ_E_CORRUPT;
+        at += 2 + cb;
+        const int64_t initial_pos = at;
+        int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
+        std::vector<ArcBlock> blocks[2];
+        int64_t stream_len[2] = { 0, 0 };
+        rc = list_stream(mrz, n, initial_pos, initial_pos, cb, blocks[0], &stream_len[0], &end_max);
+        if (!rc) rc = list_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, blocks[1], &stream_len[1], &end_max);
+        if (rc) return rc;
+        int64_t s0_lz4 = 0;
+        for (const ArcBlock &b : blocks[0])
+            if (b.ctype == kCtypeLz4) s0_lz4 += b.u_len;
+        const bool s0_on_device = s0_lz4 > 0;
+        // stream 0 and the chunk's length: on the device where it holds an LZ4 block (decoded whole: the parse needs
+        // every record), otherwise gathered and walked on the host as mrz_runzip_buffer_range does
+        DeviceStreams ds;
+        int64_t chunk_len = 0;
+        s0.clear();
+        if (s0_on_device) {
+            if (blocks[0].size() > 0x7fffffffu) return MRZ_E_UNSUPPORTED;
+            rc = open_ctx();
+            if (rc) return rc;
+            const std::vector<ArcBlock> only0[2] = { blocks[0], std::vector<ArcBlock>() };
+            const int64_t len0[2] = { stream_len[0], 0 };
+            rc = build_device_streams(g.ctx, only0, len0, ds);
+            if (rc) return rc;
+            acc.s0_lz4_bytes += s0_lz4;
+            mrz_range_info ri;
+            rc = mrz_runzip_origins(g.ctx, ds.s0, stream_len[0], stream_len[1], MRZ_MEM_DEVICE, cb, 0, 0, nullptr,
+                                    MRZ_MEM_DEVICE, &ri);
+            if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // too short to hold a terminator
+            if (rc) return rc;
+            chunk_len = ri.chunk_len;
+        } else {
+            for (const ArcBlock &b : blocks[0]) s0.insert(s0.end(), b.p, b.p + b.c_len);
+            if (!records_out_len(s0, cb, &chunk_len)) return MRZ_E_CORRUPT;
+        }
+        if (!bad_range && count > 0 && total < first + count && total + chunk_len > first) {
+            const int64_t a = first > total ? first : total;
+            const int64_t b = first + count < total + chunk_len ? first + count : total + chunk_len;
+            rc = open_ctx();
+            if (rc) return rc;
+            if (!d_out) {
+                if (hipMalloc((void **)&scratch.p, (size_t)count) != hipSuccess) return MRZ_E_NOMEM;
+                d_out = scratch.p;
+            }
+            rc = range_chunk_blocks(g.ctx, cus, s0_on_device ? (const void *)ds.s0 : (const void *)s0.data(),
+                                    s0_on_device ? stream_len[0] : (int64_t)s0.size(),
+                                    s0_on_device ? MRZ_MEM_DEVICE : MRZ_MEM_HOST, blocks[1], stream_len[1], cb, a - total,
+                                    b - a, d_out + (a - first), acc);
+            if (rc) return rc;
+        }
+        total += chunk_len;
+        at = end_max;
+        if (size_known && total >= first + count) break;  // the range is covered
+        if (eof) break;
+    }
+    if (!size_known) {
+        if (file_len) *file_len = total;
+        if (first < 0 || count < 0 || first > total || count > total - first) return MRZ_E_ARG;
+    } else if (total < first + count)
+        return MRZ_E_CORRUPT;  // fewer bytes than the header promised
+    if (!count) return MRZ_OK;
+    if (!out) return MRZ_E_ARG;
+    if (scratch.p && hipMemcpy(out, scratch.p, (size_t)count, hipMemcpyDeviceToHost) != hipSuccess) return MRZ_E_HIP;
+    return MRZ_OK;
+}
+
+extern "C" int mrz_runzip_buffer_range_ex(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out,
+                                          int out_where, int64_t *file_len, mrz_archive_range_info *info) {
+    mrz_archive_range_info acc;
+    memset(&acc, 0, sizeof(acc));
+    int rc;
+    try {
+        rc = runzip_buffer_range_ex_impl(device, mrz_v, n, first, count, out, out_where, file_len, acc);
+    } catch (const std::bad_alloc &) {
+        rc = MRZ_E_NOMEM;
+    } catch (const std::length_error &) {
+        rc = MRZ_E_CORRUPT;
+    }
+    if (info) *info = acc;
+    return rc;
 }

@@ -52,4 +52,14 @@ size_t mrz_crc_tables_size(void);
 int64_t mrz_crc32_parts_needed(int64_t n);
 hipError_t mrz_launch_crc32(hipStream_t stream, const uint8_t *buf, int64_t n, const mrz_crc_tables *tb, uint32_t *parts,
                             uint32_t *crc_out);
+// range decode over a blocked stream 1 (mrz_runzip.hip): per block the lowest / highest in-block offset among `count`
+// origins in device memory (span preset to lo = ~0, hi = 0), and the gather from the staged pieces of the touched blocks
+struct mrz_uz_span {
+    uint32_t lo, hi;
+};
+hipError_t mrz_launch_block_span(hipStream_t stream, int cus, const int64_t *origins, int64_t count, const int64_t *starts,
+                                 int64_t nblocks, mrz_uz_span *span);
+hipError_t mrz_launch_block_gather(hipStream_t stream, int cus, const int64_t *origins, int64_t count,
+                                   const int64_t *starts, int64_t nblocks, const mrz_uz_span *span, const int64_t *base,
+                                   const uint8_t *staged, uint8_t *out);
 }

@@ -342,8 +342,24 @@ __global__ __launch_bounds__(64) void mrz_lz4_compress_kernel(const uint8_t *con
 // A match reads bytes that this wave stored for earlier sequences, possibly the previous instruction's.  The stores
 // of one wave are ordered before its later loads by the workgroup barrier (vmcnt(0) + s_barrier; the block is this one
 // wave), as in mrz_uz_decode_kernel; `synced` skips the barrier when the source lies in bytes that are ordered already.
+//
+// PREFIX: the first `want` bytes only (0 <= want <= u_len; the whole-block instantiation ignores `want`).  The walk and
+// its accept rules are the same, against the block's real c_len and u_len.  The copy -- a literal run or a match --
+// with which the produced count reaches `want` is validated as the full decoder validates it before it copies (lengths
+// against both buffers, the last-sequence rule and, for that last sequence, that it ends at u_len; for a match the
+// offset, the u_len - 5 rule or the shortcut's conditions); then it is cut at `want` and the wave returns 0.  Exactly
+// `want` bytes are stored, nothing at or beyond dst + want, and no load leaves [src, src + c_len).  want == u_len is
+// the full decoder: it walks on to the end of the input.  want == 0 < u_len touches nothing and returns 0.
+// THE CONTRACT: a reject that the full walk meets only behind that copy is not seen.  (Range decode makes the same
+// trade for the CRC.)
+template <bool PREFIX>
 __device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64_t c_len, uint8_t *dst, int64_t u_len,
-                                          int lane) {
+                                          int64_t want, int lane) {
+    if constexpr (PREFIX)
+        if (want == 0 && u_len > 0) return 0;
+    // where the walk ends: a whole block is walked to the end of its input, as the full decoder walks it
+    const int64_t cut = PREFIX && want < u_len ? want : u_len + 1;
+    (void)cut;
     if (c_len <= 0 || u_len < 0) return 1;
     if (u_len == 0) return c_len == 1 && src[0] == 0 ? 0 : 1;
     int64_t ip = 0, op = 0, synced = 0;
@@ -356,6 +372,11 @@ __device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64
         int64_t offset;
         bool checked = false;  // the shortcut: 0..14 literals and a short match far from both ends
         if (lit != 15 && ip < c_len - 16 && op <= u_len - 32) {
+            if constexpr (PREFIX)
+                if (op + lit >= cut) {
+                    for (int64_t j = lane; j < cut - op; j += 64) dst[op + j] = src[ip + j];
+                    return 0;
+                }
             for (int64_t j = lane; j < lit; j += 64) dst[op + j] = src[ip + j];
             ip += lit;
             op += lit;
@@ -389,9 +410,20 @@ __device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64
             if (lit > c_len - ip || lit > u_len - op) return 1;
             if (op + lit > u_len - 12 || ip + lit > c_len - 8) {  // must be the last sequence
                 if (ip + lit != c_len) return 1;
+                if constexpr (PREFIX)
+                    if (op + lit >= cut) {
+                        if (op + lit != u_len) return 1;
+                        mrz_lz_copy(dst + op, src + ip, cut - op, lane);
+                        return 0;
+                    }
                 mrz_lz_copy(dst + op, src + ip, lit, lane);
                 return op + lit == u_len ? 0 : 1;
             }
+            if constexpr (PREFIX)
+                if (op + lit >= cut) {
+                    mrz_lz_copy(dst + op, src + ip, cut - op, lane);
+                    return 0;
+                }
             mrz_lz_copy(dst + op, src + ip, lit, lane);
             ip += lit;
             op += lit;
@@ -422,6 +454,8 @@ __device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64
         if (ml > u_len - op) return 1;
         if (!checked && op + ml > u_len - 5) return 1;
         const int64_t from = op - offset;
+        if constexpr (PREFIX)
+            if (ml > cut - op) ml = cut - op;  // validated whole, copied as far as `want`
         if ((offset < ml ? op : from + ml) > synced) {
             __syncthreads();
             synced = op;
@@ -438,6 +472,8 @@ __device__ static int mrz_lz4_decode_wave(const uint8_t *__restrict__ src, int64
             }
         }
         op += ml;
+        if constexpr (PREFIX)
+            if (op >= cut) return 0;
     }
 }
 
@@ -448,7 +484,20 @@ __global__ __launch_bounds__(64) void mrz_lz4_decode_kernel(const uint8_t *const
                                                             int *__restrict__ status) {
     const int i = blockIdx.x;
     if (i >= count) return;
-    const int r = mrz_lz4_decode_wave(bufs[i], c_lens[i], outs[i], u_lens[i], threadIdx.x);
+    const int r = mrz_lz4_decode_wave<false>(bufs[i], c_lens[i], outs[i], u_lens[i], u_lens[i], threadIdx.x);
+    if (threadIdx.x == 0) status[i] = r ? MRZ_E_CORRUPT : 0;
+}
+
+// the first wants[i] bytes of every block
+__global__ __launch_bounds__(64) void mrz_lz4_decode_prefix_kernel(const uint8_t *const *__restrict__ bufs,
+                                                                   const int64_t *__restrict__ c_lens,
+                                                                   uint8_t *const *__restrict__ outs,
+                                                                   const int64_t *__restrict__ u_lens,
+                                                                   const int64_t *__restrict__ wants, int count,
+                                                                   int *__restrict__ status) {
+    const int i = blockIdx.x;
+    if (i >= count) return;
+    const int r = mrz_lz4_decode_wave<true>(bufs[i], c_lens[i], outs[i], u_lens[i], wants[i], threadIdx.x);
     if (threadIdx.x == 0) status[i] = r ? MRZ_E_CORRUPT : 0;
 }
 
@@ -579,9 +628,10 @@ static int mrz_lz4_reserve(mrz_ctx *ctx, int64_t need) {
     return MRZ_OK;
 }
 
-// Shared by both directions.  scratch layout: in ptrs | in lens | out ptrs | out lens | results (8 B per block each)
-// | staged inputs (where == host) | staged outputs (out_where == host), every block on a 16-byte boundary.
-// in_lens[i] bytes are read from bufs[i]; out_room[i] bytes may be written at outs[i].
+// Shared by both directions.  scratch layout: in ptrs | in lens | out ptrs | out lens | results | extra (8 B per block
+// each) | staged inputs (where == host) | staged outputs (out_where == host), every block on a 16-byte boundary.
+// in_lens[i] bytes are read from bufs[i]; out_room[i] bytes may be written at outs[i]; `extra` (may be null) is one
+// more column of the caller's (the prefix decode's u_lens).
 struct mrz_lz4_job {
     uint8_t *base;
     int64_t in_at, out_at;
@@ -590,13 +640,14 @@ struct mrz_lz4_job {
 };
 
 static int mrz_lz4_stage(mrz_ctx *ctx, mrz_lz4_job &job, const void *const *bufs, const int64_t *in_lens, int count,
-                         int where, void *const *outs, const int64_t *out_room, int out_where) {
+                         int where, void *const *outs, const int64_t *out_room, int out_where,
+                         const int64_t *extra = nullptr) {
     int64_t in_total = 0, out_total = 0;
     for (int i = 0; i < count; i++) {
         in_total += (in_lens[i] + 31) & ~15ll;
         out_total += (out_room[i] + 31) & ~15ll;
     }
-    const int64_t hdr = (int64_t)count * 40;
+    const int64_t hdr = (int64_t)count * 48;
     job.in_at = (hdr + 15) & ~15ll;
     job.out_at = job.in_at + (where == MRZ_MEM_HOST ? in_total : 0);
     const int rc = mrz_lz4_reserve(ctx, job.out_at + (out_where == MRZ_MEM_HOST ? out_total : 0) + 64);
@@ -625,6 +676,7 @@ static int mrz_lz4_stage(mrz_ctx *ctx, mrz_lz4_job &job, const void *const *bufs
     if (e == hipSuccess) e = hipMemcpyAsync(job.base + col, in_lens, col, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(job.base + 2 * col, job.out_ptr.data(), col, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(job.base + 3 * col, out_room, col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && extra) e = hipMemcpyAsync(job.base + 5 * col, extra, col, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host arrays are the caller's and ours
     if (e != hipSuccess) {
         ctx->last_err = e;
@@ -708,6 +760,45 @@ extern "C" int mrz_lz4_decompress_batch(mrz_ctx *ctx, const void *const *bufs, c
                 if (!status[i] && u_lens[i])
                     HIPCHK(ctx, hipMemcpyAsync(outs[i], job.out_ptr[(size_t)i], (size_t)u_lens[i],
                                                hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+    return MRZ_OK;
+}
+
+extern "C" int mrz_lz4_decompress_prefix_batch(mrz_ctx *ctx, const void *const *bufs, const int64_t *c_lens, int count,
+                                               int where, void *const *outs, const int64_t *u_lens, const int64_t *wants,
+                                               int out_where, int32_t *status) {
+    int rc = mrz_lz4_batch_args(ctx, bufs, c_lens, count, where, outs, u_lens, out_where, status);
+    if (rc) return rc;
+    if (count && !wants) return MRZ_E_ARG;
+    if (!count) return MRZ_OK;
+    try {
+        for (int i = 0; i < count; i++) {
+            if (c_lens[i] < 0 || c_lens[i] > 0x7E000000ll || (c_lens[i] && !bufs[i])) return MRZ_E_ARG;
+            if (u_lens[i] < 0 || u_lens[i] > 0x7E000000ll) return MRZ_E_ARG;
+            if (wants[i] < 0 || wants[i] > u_lens[i] || (wants[i] && !outs[i])) return MRZ_E_ARG;
+        }
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        mrz_lz4_job job;
+        rc = mrz_lz4_stage(ctx, job, bufs, c_lens, count, where, outs, wants, out_where, u_lens);
+        if (rc) return rc;
+        const size_t col = (size_t)count * 8;
+        int *d_res = (int *)(job.base + 4 * col);
+        hipLaunchKernelGGL(mrz_lz4_decode_prefix_kernel, dim3((unsigned)count), dim3(64), 0, ctx->stream,
+                           (const uint8_t *const *)job.base, (const int64_t *)(job.base + col),
+                           (uint8_t *const *)(job.base + 2 * col), (const int64_t *)(job.base + 5 * col),
+                           (const int64_t *)(job.base + 3 * col), count, d_res);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(status, d_res, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (out_where == MRZ_MEM_HOST) {  // a rejected block's bytes are unspecified: they stay on the device
+            for (int i = 0; i < count; i++)
+                if (!status[i] && wants[i])
+                    HIPCHK(ctx, hipMemcpyAsync(outs[i], job.out_ptr[(size_t)i], (size_t)wants[i], hipMemcpyDeviceToHost,
+                                               ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
     } catch (const std::bad_alloc &) {

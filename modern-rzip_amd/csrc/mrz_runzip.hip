@@ -503,6 +503,103 @@ __global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_resolve_kernel(const mr
     }
 }
 
+// ---- range decode over a stream 1 that stays in its blocks (mrz_runzip_buffer_range_ex) ---------------------------
+// The origins of a range stay on the device; `starts` is the table of the chunk's stream-1 blocks as ascending offsets
+// in stream 1, starts[0] == 0 (an empty block shares its start with its successor and is never found).
+
+// the block that holds stream-1 offset x: the last b with starts[b] <= x
+__device__ __forceinline__ int64_t mrz_uz_block_of(const int64_t *__restrict__ starts, int64_t nblocks, int64_t x) {
+    int64_t lo = 0, hi = nblocks - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (starts[mid] <= x)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// span[b] = the lowest and highest in-block offset that any origin asks of block b (the host presets lo = ~0, hi = 0:
+// an untouched block keeps lo > hi; no block is longer than 2^32).  Consecutive output bytes mostly have consecutive
+// origins, so the 64 origins of a wave fall into one or two blocks: the wave reduces per distinct block (one round of
+// shuffles each) and its leader issues the two atomics.
+__global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_block_span_kernel(const int64_t *__restrict__ origins,
+                                                                           int64_t count,
+                                                                           const int64_t *__restrict__ starts,
+                                                                           int64_t nblocks,
+                                                                           mrz_uz_span *__restrict__ span) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t stride = (int64_t)gridDim.x * MRZ_UZ_THREADS;
+    const int64_t base0 = mrz_uz_uniform64((int64_t)blockIdx.x * MRZ_UZ_THREADS + (threadIdx.x - lane));
+    for (int64_t base = base0; base < count; base += stride) {
+        const int64_t i = base + lane;
+        int64_t b = -1;
+        uint32_t off = 0;
+        if (i < count) {
+            const int64_t x = origins[i];
+            b = mrz_uz_block_of(starts, nblocks, x);
+            off = (uint32_t)(x - starts[b]);
+        }
+        mrz_u64 todo = __ballot(i < count);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int64_t bl = mrz_bcast64(b, leader);
+            const bool mine = b == bl;
+            uint32_t lo = mine ? off : 0xffffffffu, hi = mine ? off : 0u;
+            for (int d = 32; d; d >>= 1) {
+                const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, d, MRZ_WAVE), h2 = (uint32_t)__shfl_xor((int)hi, d, MRZ_WAVE);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+            if (lane == leader) {
+                atomicMin(&span[bl].lo, lo);
+                atomicMax(&span[bl].hi, hi);
+            }
+            todo &= ~__ballot(mine);
+        }
+    }
+}
+
+// out[i] = staged[base[b] + (in-block offset of origin i) - span[b].lo], b the origin's block: `staged` holds, for every
+// touched block, its bytes from in-block offset span[b].lo on at staged + base[b]
+__global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_block_gather_kernel(const int64_t *__restrict__ origins,
+                                                                             int64_t count,
+                                                                             const int64_t *__restrict__ starts,
+                                                                             int64_t nblocks,
+                                                                             const mrz_uz_span *__restrict__ span,
+                                                                             const int64_t *__restrict__ base,
+                                                                             const uint8_t *__restrict__ staged,
+                                                                             uint8_t *__restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * MRZ_UZ_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * MRZ_UZ_THREADS + threadIdx.x; i < count; i += stride) {
+        const int64_t x = origins[i];
+        const int64_t b = mrz_uz_block_of(starts, nblocks, x);
+        out[i] = staged[base[b] + (x - starts[b]) - (int64_t)span[b].lo];
+    }
+}
+
+static unsigned uz_block_grid(int cus, int64_t count) {
+    int64_t grid = (int64_t)(cus > 0 ? cus : 64) * 8;
+    const int64_t blocks = (count + MRZ_UZ_THREADS - 1) / MRZ_UZ_THREADS;
+    return (unsigned)(grid > blocks ? blocks : grid);
+}
+
+extern "C" hipError_t mrz_launch_block_span(hipStream_t stream, int cus, const int64_t *origins, int64_t count,
+                                            const int64_t *starts, int64_t nblocks, mrz_uz_span *span) {
+    hipLaunchKernelGGL(mrz_uz_block_span_kernel, dim3(uz_block_grid(cus, count)), dim3(MRZ_UZ_THREADS), 0, stream, origins,
+                       count, starts, nblocks, span);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t mrz_launch_block_gather(hipStream_t stream, int cus, const int64_t *origins, int64_t count,
+                                              const int64_t *starts, int64_t nblocks, const mrz_uz_span *span,
+                                              const int64_t *base, const uint8_t *staged, uint8_t *out) {
+    hipLaunchKernelGGL(mrz_uz_block_gather_kernel, dim3(uz_block_grid(cus, count)), dim3(MRZ_UZ_THREADS), 0, stream,
+                       origins, count, starts, nblocks, span, base, staged, out);
+    return hipGetLastError();
+}
+
 static int uz_grow(mrz_ctx *ctx, int64_t want) {
     return mrz_grow(ctx, (uint8_t **)&ctx->rz_scratch, &ctx->rz_scratch_cap, want);
 }
