@@ -3,13 +3,13 @@
 // block framing, magic header, whole-file MD5 on a helper thread (the
 // reference also keeps the checksums off the matcher's thread,
 // src/rzip.c:488-505).  MD5 is a strictly serial hash; it overlaps the GPU work.
+// The decompress side (`mrzip -d`) is mrz_unarchive.hip.
 #include <errno.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <new>
-#include <stdexcept>
 
 #include <condition_variable>
 #include <deque>
@@ -29,92 +29,13 @@ struct mrz_join_guard {
 
 #include "../../include/mrzgpu_host.h"
 #include "mrz_ctx.h"
+#include "mrz_md5.h"
 
 namespace {
 
 const int64_t kMiB = 1048576;
 const int64_t kStreamMin = 10 * kMiB;   // STREAM_BUFSIZE, include/mrzip_private.h:27
 const int64_t kChunkUnit = 100 * kMiB;  // CHUNK_MULTIPLE, src/rzip.c:46
-
-// ---- MD5 (RFC 1321; libgcrypt GCRY_MD_MD5 in the reference) ---------------
-struct Md5 {
-    uint32_t h[4];
-    uint64_t total;
-    uint8_t pend[64];
-    size_t npend;
-    Md5() : total(0), npend(0) {
-        h[0] = 0x67452301u;
-        h[1] = 0xefcdab89u;
-        h[2] = 0x98badcfeu;
-        h[3] = 0x10325476u;
-    }
-    static uint32_t rol(uint32_t x, int s) { return (x << s) | (x >> (32 - s)); }
-    void block(const uint8_t *p) {
-        static const uint32_t K[64] = {
-            0xd76aa478, 0xe8c7b756, 0x242070db, 0xc1bdceee, 0xf57c0faf, 0x4787c62a, 0xa8304613, 0xfd469501,
-            0x698098d8, 0x8b44f7af, 0xffff5bb1, 0x895cd7be, 0x6b901122, 0xfd987193, 0xa679438e, 0x49b40821,
-            0xf61e2562, 0xc040b340, 0x265e5a51, 0xe9b6c7aa, 0xd62f105d, 0x02441453, 0xd8a1e681, 0xe7d3fbc8,
-            0x21e1cde6, 0xc33707d6, 0xf4d50d87, 0x455a14ed, 0xa9e3e905, 0xfcefa3f8, 0x676f02d9, 0x8d2a4c8a,
-            0xfffa3942, 0x8771f681, 0x6d9d6122, 0xfde5380c, 0xa4beea44, 0x4bdecfa9, 0xf6bb4b60, 0xbebfbc70,
-            0x289b7ec6, 0xeaa127fa, 0xd4ef3085, 0x04881d05, 0xd9d4d039, 0xe6db99e5, 0x1fa27cf8, 0xc4ac5665,
-            0xf4292244, 0x432aff97, 0xab9423a7, 0xfc93a039, 0x655b59c3, 0x8f0ccc92, 0xffeff47d, 0x85845dd1,
-            0x6fa87e4f, 0xfe2ce6e0, 0xa3014314, 0x4e0811a1, 0xf7537e82, 0xbd3af235, 0x2ad7d2bb, 0xeb86d391 };
-        static const int S[4][4] = { { 7, 12, 17, 22 }, { 5, 9, 14, 20 }, { 4, 11, 16, 23 }, { 6, 10, 15, 21 } };
-        uint32_t m[16];
-        memcpy(m, p, 64);  // little-endian host
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3];
-        for (int i = 0; i < 64; i++) {
-            const int r = i >> 4;
-            uint32_t f;
-            int g;
-            switch (r) {
-                case 0: f = d ^ (b & (c ^ d)); g = i; break;
-                case 1: f = c ^ (d & (b ^ c)); g = (5 * i + 1) & 15; break;
-                case 2: f = b ^ c ^ d; g = (3 * i + 5) & 15; break;
-                default: f = c ^ (b | ~d); g = (7 * i) & 15; break;
-            }
-            const uint32_t nb = b + rol(a + f + K[i] + m[g], S[r][i & 3]);
-            a = d;
-            d = c;
-            c = b;
-            b = nb;
-        }
-        h[0] += a;
-        h[1] += b;
-        h[2] += c;
-        h[3] += d;
-    }
-    void update(const uint8_t *p, size_t n) {
-        total += n;
-        if (npend) {
-            size_t take = 64 - npend;
-            if (take > n) take = n;
-            memcpy(pend + npend, p, take);
-            npend += take;
-            p += take;
-            n -= take;
-            if (npend < 64) return;
-            block(pend);
-            npend = 0;
-        }
-        for (; n >= 64; p += 64, n -= 64) block(p);
-        if (n) {
-            memcpy(pend, p, n);
-            npend = n;
-        }
-    }
-    void finish(uint8_t out[16]) {
-        const uint64_t bits = total * 8;
-        uint8_t tail[128];
-        size_t k = npend;
-        memcpy(tail, pend, k);
-        tail[k++] = 0x80;
-        while (k % 64 != 56) tail[k++] = 0;
-        for (int i = 0; i < 8; i++) tail[k++] = (uint8_t)(bits >> (8 * i));
-        for (size_t o = 0; o < k; o += 64) block(tail + o);
-        memcpy(out, h, 16);
-    }
-};
 
 int64_t page_floor(int64_t v, int64_t page) {  // round_to_page, src/util.c:166-169
     v -= v % page;
@@ -959,673 +880,4 @@ extern "C" int mrz_rzip_pipeline(const mrz_control *ctl, const void *in_v, int64
     } catch (const std::bad_alloc &) {
         return MRZ_E_NOMEM;
     }
-}
-
-// ---- decompress side: `mrzip -d` of a -n archive (runzip_fd, src/runzip.c:332-437) -----------------
-namespace {
-
-int64_t peek_le(const uint8_t *p, int nbytes) {
-    uint64_t v = 0;
-    for (int i = 0; i < nbytes; i++) v |= (uint64_t)p[i] << (8 * i);
-    return (int64_t)v;
-}
-
-// follows one stream's block chain (fill_buffer, src/stream.c:1412-1571) and hands every payload to block(p, len);
-// only CTYPE_NONE (3) blocks.  This is the walk of mrz_runzip_buffer_range, which gathers bytes straight from the
-// archive's blocks: range decode over LZ4 blocks is out of scope, such an archive gets MRZ_E_UNSUPPORTED there
-// (mrz_runzip_buffer reads it: list_stream below).
-// Ranges of an archive with LZ4 blocks: mrz_runzip_buffer_range_ex, at the end of this file.
-template <class F>
-int walk_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, F &&block, int64_t *end_max) {
-    int64_t at = head_at;
-    for (;;) {
-        if (at + 1 + 3 * cb > n) return MRZ_E_CORRUPT;
-        const int ctype = mrz[at];
-        const int64_t c_len = peek_le(mrz + at + 1, cb), u_len = peek_le(mrz + at + 1 + cb, cb);
-        const int64_t next = peek_le(mrz + at + 1 + 2 * cb, cb);
-        if (ctype != 3) return MRZ_E_UNSUPPORTED;
-        if (c_len != u_len || c_len < 0) return MRZ_E_CORRUPT;
-        const int64_t pay = at + 1 + 3 * cb;
-        if (c_len > n - pay) return MRZ_E_CORRUPT;  // (compared without adding: a length field may be 2^63 - 1)
-        block(mrz + pay, c_len);
-        if (pay + c_len > *end_max) *end_max = pay + c_len;
-        if (!next) return MRZ_OK;
-        if (next < 0 || next > n - initial_pos || initial_pos + next <= at) return MRZ_E_CORRUPT;  // chains only run forward
-        at = initial_pos + next;
-    }
-}
-
-// ... and concatenates the payloads
-int gather_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, std::vector<uint8_t> &dst,
-                  int64_t *end_max) {
-    return walk_stream(mrz, n, initial_pos, head_at, cb,
-                       [&](const uint8_t *p, int64_t len) { dst.insert(dst.end(), p, p + len); }, end_max);
-}
-
-// One block of a stream as mrz_runzip_buffer takes it: CTYPE_NONE (3), or CTYPE_LZ4 (5) as `mrzip -l` writes it
-// (lz4_compress_buf / lz4_decompress_buf, src/stream.c:278-312,465-477).
-struct ArcBlock {
-    int ctype;
-    const uint8_t *p;
-    int64_t c_len, u_len;
-};
-
-const int kCtypeNone = 3, kCtypeLz4 = 5;
-const int64_t kLz4MaxInput = 0x7E000000ll;
-
-// walk_stream for mrz_runzip_buffer: the chain's blocks in order, *total their decoded length
-int list_stream(const uint8_t *mrz, int64_t n, int64_t initial_pos, int64_t head_at, int cb, std::vector<ArcBlock> &blocks,
-                int64_t *total, int64_t *end_max) {
-    int64_t at = head_at;
-    *total = 0;
-    for (;;) {
-        if (at + 1 + 3 * cb > n) return MRZ_E_CORRUPT;
-        const int ctype = mrz[at];
-        const int64_t c_len = peek_le(mrz + at + 1, cb), u_len = peek_le(mrz + at + 1 + cb, cb);
-        const int64_t next = peek_le(mrz + at + 1 + 2 * cb, cb);
-        if (ctype != kCtypeNone && ctype != kCtypeLz4) return MRZ_E_UNSUPPORTED;
-        if (c_len < 0 || u_len < 0) return MRZ_E_CORRUPT;
-        if (ctype == kCtypeNone && c_len != u_len) return MRZ_E_CORRUPT;
-        const int64_t pay = at + 1 + 3 * cb;
-        if (c_len > n - pay) return MRZ_E_CORRUPT;  // (compared without adding: a length field may be 2^63 - 1)
-        if (ctype == kCtypeLz4) {
-            if (u_len > kLz4MaxInput) return MRZ_E_UNSUPPORTED;
-            // no LZ4 block is longer than LZ4_compressBound of what it holds, and none holds more than 255 bytes per
-            // byte of its own (a length byte adds at most 255): whatever claims otherwise is not worth an allocation
-            if (c_len > u_len + u_len / 255 + 16 || u_len / 255 > c_len) return MRZ_E_CORRUPT;
-        }
-        blocks.push_back(ArcBlock{ ctype, mrz + pay, c_len, u_len });
-        *total += u_len;
-        if (pay + c_len > *end_max) *end_max = pay + c_len;
-        if (!next) return MRZ_OK;
-        if (next < 0 || next > n - initial_pos || initial_pos + next <= at) return MRZ_E_CORRUPT;  // chains only run forward
-        at = initial_pos + next;
-    }
-}
-
-// The two streams of a chunk that holds LZ4 blocks, put together in device memory: CTYPE_NONE payloads are copied
-// into place, LZ4 payloads are uploaded as they are and decoded into place by mrz_lz4_decompress_batch, all blocks of
-// both streams in one launch.  What the blocks decode to never exists in host memory.
-struct DeviceStreams {
-    uint8_t *base = nullptr, *s0 = nullptr, *s1 = nullptr;
-    ~DeviceStreams() {
-        if (base) hipFree(base);
-    }
-};
-
-int build_device_streams(mrz_ctx *ctx, const std::vector<ArcBlock> (&blocks)[2], const int64_t (&total)[2],
-                         DeviceStreams &ds) {
-    int64_t packed = 0;
-    for (int s = 0; s < 2; s++)
-        for (const ArcBlock &b : blocks[s])
-            if (b.ctype == kCtypeLz4) packed += (b.c_len + 31) & ~15ll;
-    const int64_t at1 = (total[0] + 64 + 255) & ~255ll, at_packed = at1 + ((total[1] + 64 + 255) & ~255ll);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (hipMalloc((void **)&ds.base, (size_t)(at_packed + packed + 64)) != hipSuccess) return MRZ_E_NOMEM;
-    ds.s0 = ds.base;
-    ds.s1 = ds.base + at1;
-    std::vector<const void *> src;
-    std::vector<void *> dst;
-    std::vector<int64_t> c_lens, u_lens;
-    int64_t pk = at_packed;
-    for (int s = 0; s < 2; s++) {
-        uint8_t *w = s ? ds.s1 : ds.s0;
-        for (const ArcBlock &b : blocks[s]) {
-            if (b.ctype == kCtypeLz4) {
-                if (b.c_len)
-                    HIPCHK(ctx, hipMemcpyAsync(ds.base + pk, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, ctx->stream));
-                src.push_back(ds.base + pk);
-                dst.push_back(w);
-                c_lens.push_back(b.c_len);
-                u_lens.push_back(b.u_len);
-                pk += (b.c_len + 31) & ~15ll;
-            } else if (b.c_len)
-                HIPCHK(ctx, hipMemcpyAsync(w, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, ctx->stream));
-            w += b.u_len;
-        }
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> status(src.size());
-    const int rc = mrz_lz4_decompress_batch(ctx, src.data(), c_lens.data(), (int)src.size(), MRZ_MEM_DEVICE, dst.data(),
-                                            u_lens.data(), MRZ_MEM_DEVICE, status.data());
-    if (rc) return rc;
-    for (int32_t st : status)
-        if (st) return MRZ_E_CORRUPT;
-    return MRZ_OK;
-}
-
-// bytes a chunk decodes to: the lengths of its records (host side: 3 or 3 + cb bytes each); false without a terminator
-bool records_out_len(const std::vector<uint8_t> &s0, int cb, int64_t *out_len) {
-    int64_t need = 0, i = 0;
-    const int64_t n0 = (int64_t)s0.size();
-    while (i + 3 <= n0) {
-        const int64_t len = s0[(size_t)i + 1] | (int64_t)s0[(size_t)i + 2] << 8;
-        if (s0[(size_t)i] == 0) {
-            if (len == 0) {
-                *out_len = need;
-                return true;
-            }
-            i += 3;
-        } else
-            i += 3 + cb;
-        need += len;
-    }
-    return false;
-}
-
-// the magic header (read_magic, src/mrzip.c:225-321): the size it carries (0: none) and the hash in use
-int read_archive_header(const uint8_t *mrz, int64_t n, int64_t *expected, int *hash_code) {
-    if (n < 20 || memcmp(mrz, "MRZI", 4)) return MRZ_E_CORRUPT;
-    if (mrz[15]) return MRZ_E_UNSUPPORTED;  // encrypted
-    *expected = peek_le(mrz + 6, 8);
-    *hash_code = mrz[14];
-    if (*hash_code != 0 && *hash_code != 1) return MRZ_E_UNSUPPORTED;  // MD5 (default) or CRC only
-    return MRZ_OK;
-}
-
-}  // namespace
-
-static int runzip_buffer_impl(int device, const void *mrz_v, int64_t n, void **out, int64_t *out_len) {
-    if (!mrz_v || !out || !out_len) return MRZ_E_ARG;
-    const uint8_t *mrz = (const uint8_t *)mrz_v;
-    int64_t expected = 0;
-    int hash_code = 0;
-    int rc = read_archive_header(mrz, n, &expected, &hash_code);
-    if (rc) return rc;
-    // an archive written to STDOUT in several chunks carries no size (src/mrzip.c:137-140): grow chunk by chunk
-    const bool size_known = expected > 0;
-    int64_t cap = size_known ? expected : 0;
-    uint8_t *res = (uint8_t *)malloc((size_t)(cap > 0 ? cap : 1));
-    if (!res) return MRZ_E_NOMEM;
-    mrz_ctx *ctx = nullptr;
-    rc = mrz_open(&ctx, device, 7, 0);
-    int64_t at = 20 + mrz[19], total = 0;
-    std::vector<uint8_t> s0, s1;
-    while (!rc) {  // runzip_chunk, src/runzip.c:226-330
-        if (at + 2 > n) {
-            rc = MRZ_E_CORRUPT;
-            break;
-        }
-        const int cb = mrz[at], eof = mrz[at + 1];
-        if (cb < 1 || cb > 8 || at + 2 + cb > n) {
-            rc = MRZ_E_CORRUPT;
-            break;
-        }
-        at += 2 + cb;  // chunk_bytes, eof, chunk size (the field is chunk_bytes wide: a chunk below one page does
-                       // not fit its own size there, src/stream.c:779-780,1224 -- so it is not used for sizing)
-        const int64_t initial_pos = at;
-        int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
-        s0.clear();
-        s1.clear();
-        std::vector<ArcBlock> blocks[2];
-        int64_t stream_len[2] = { 0, 0 };
-        rc = list_stream(mrz, n, initial_pos, initial_pos, cb, blocks[0], &stream_len[0], &end_max);
-        if (!rc) rc = list_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, blocks[1], &stream_len[1], &end_max);
-        if (rc) break;
-        bool packed = false;
-        for (int s = 0; s < 2; s++)
-            for (const ArcBlock &b : blocks[s]) packed = packed || b.ctype != kCtypeNone;
-        DeviceStreams ds;
-        if (packed) {
-            if (blocks[0].size() + blocks[1].size() > 0x7fffffffu) {
-                rc = MRZ_E_UNSUPPORTED;
-                break;
-            }
-            rc = build_device_streams(ctx, blocks, stream_len, ds);
-            if (rc) break;
-            if (!size_known) {  // the one case in which stream 0 (the records, not the literals) comes back: its
-                                // records say how much room the chunk needs
-                s0.resize((size_t)stream_len[0]);
-                if (stream_len[0] &&
-                    hipMemcpy(s0.data(), ds.s0, (size_t)stream_len[0], hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc = MRZ_E_HIP;
-                    break;
-                }
-            }
-        } else {
-            for (const ArcBlock &b : blocks[0]) s0.insert(s0.end(), b.p, b.p + b.c_len);
-            for (const ArcBlock &b : blocks[1]) s1.insert(s1.end(), b.p, b.p + b.c_len);
-        }
-        if (!size_known) {
-            int64_t need = 0;
-            if (!records_out_len(s0, cb, &need)) {
-                rc = MRZ_E_CORRUPT;
-                break;
-            }
-            if (total + need > cap) {
-                uint8_t *r2 = (uint8_t *)realloc(res, (size_t)(total + need > 0 ? total + need : 1));
-                if (!r2) {
-                    rc = MRZ_E_NOMEM;
-                    break;
-                }
-                res = r2;
-                cap = total + need;
-            }
-        }
-        int64_t got = 0;
-        uint32_t crc_calc = 0, crc_stored = 0;
-        if (packed)
-            rc = mrz_runzip_chunk(ctx, ds.s0, stream_len[0], ds.s1, stream_len[1], MRZ_MEM_DEVICE, cb, res + total,
-                                  MRZ_MEM_HOST, cap - total, &got, &crc_calc, &crc_stored);
-        else
-            rc = mrz_runzip_chunk(ctx, s0.data(), (int64_t)s0.size(), s1.data(), (int64_t)s1.size(), MRZ_MEM_HOST, cb,
-                                  res + total, MRZ_MEM_HOST, cap - total, &got, &crc_calc, &crc_stored);
-        if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // more output than the header promised
-        if (rc) break;
-        if (!hash_code && crc_calc != crc_stored) {  // "Bad checksum", src/runzip.c:317-320 (only without a hash)
-            rc = MRZ_E_CORRUPT;
-            break;
-        }
-        total += got;
-        at = end_max;
-        if (eof) break;
-    }
-    if (ctx) mrz_close(ctx);
-    if (!rc && size_known && total != expected) rc = MRZ_E_CORRUPT;
-    if (!rc && hash_code == 1) {  // src/runzip.c:384-412
-        uint8_t d[16];
-        Md5 h;
-        h.update(res, (size_t)total);
-        h.finish(d);
-        if (at + 16 > n || memcmp(d, mrz + at, 16)) rc = MRZ_E_CORRUPT;
-    }
-    if (rc) {
-        free(res);
-        return rc;
-    }
-    *out = res;
-    *out_len = total;
-    return MRZ_OK;
-}
-
-extern "C" int mrz_runzip_buffer(int device, const void *mrz_v, int64_t n, void **out, int64_t *out_len) {
-    try {
-        return runzip_buffer_impl(device, mrz_v, n, out, out_len);
-    } catch (const std::bad_alloc &) {  // the header promises that the library never takes the host process down
-        return MRZ_E_NOMEM;
-    } catch (const std::length_error &) {
-        return MRZ_E_CORRUPT;
-    }
-}
-
-// ---- a byte range of the file a -n archive decodes to --------------------------------------------------------------
-namespace {
-
-struct StreamBlock {
-    const uint8_t *p;
-    int64_t start, len;  // stream offset of the payload's first byte
-};
-
-struct RangePart {  // a chunk that intersects the range
-    int cb;
-    std::vector<uint8_t> s0;
-    std::vector<StreamBlock> s1;  // the literal stream stays in the archive
-    int64_t s1_len;
-    int64_t lo, count;             // bytes [lo, lo + count) of the chunk ...
-    int64_t out_at;                // ... go to out_host + out_at
-};
-
-// n bytes of a stream from offset `at` through its block table
-void copy_from_blocks(const std::vector<StreamBlock> &blocks, int64_t at, int64_t n, uint8_t *dst) {
-    size_t lo = 0, hi = blocks.size();  // the last block that starts at or before `at`
-    while (hi - lo > 1) {
-        const size_t mid = (lo + hi) / 2;
-        if (blocks[mid].start <= at)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    while (n > 0) {
-        const StreamBlock &b = blocks[lo++];
-        const int64_t off = at - b.start;
-        const int64_t take = b.len - off < n ? b.len - off : n;
-        if (take > 0) memcpy(dst, b.p + off, (size_t)take);
-        dst += take;
-        at += take;
-        n -= take;
-    }
-}
-
-}  // namespace
-
-static int runzip_buffer_range_impl(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out_host,
-                                    int64_t *file_len) {
-    if (!mrz_v) return MRZ_E_ARG;
-    const uint8_t *mrz = (const uint8_t *)mrz_v;
-    int64_t expected = 0;
-    int hash_code = 0;
-    int rc = read_archive_header(mrz, n, &expected, &hash_code);
-    if (rc) return rc;
-    const bool size_known = expected > 0;
-    if (size_known) {
-        if (file_len) *file_len = expected;
-        if (first < 0 || count < 0 || first > expected || count > expected - first) return MRZ_E_ARG;
-        if (!count) return MRZ_OK;
-    }
-    // without a size the file's length is still owed to a caller whose range is wrong
-    const bool bad_range = first < 0 || count < 0 || count > INT64_MAX - first;
-    // the chunks: header, stream 0 gathered, stream 1 as a table, decoded length from the records
-    std::vector<RangePart> parts;
-    int64_t at = 20 + mrz[19], total = 0;
-    for (;;) {
-        if (at + 2 > n) return MRZ_E_CORRUPT;
-        const int cb = mrz[at], eof = mrz[at + 1];
-        if (cb < 1 || cb > 8 || at + 2 + cb > n) return MRZ_E_CORRUPT;
-        at += 2 + cb;
-        const int64_t initial_pos = at;
-        int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
-        RangePart part;
-        part.cb = cb;
-        part.s1_len = 0;
-        rc = gather_stream(mrz, n, initial_pos, initial_pos, cb, part.s0, &end_max);
-        if (!rc)
-            rc = walk_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb,
-                             [&](const uint8_t *p, int64_t len) {
-                                 part.s1.push_back(StreamBlock{ p, part.s1_len, len });
-                                 part.s1_len += len;
-                             },
-                             &end_max);
-        if (rc) return rc;
-        int64_t chunk_len = 0;
-        if (!records_out_len(part.s0, cb, &chunk_len)) return MRZ_E_CORRUPT;
-        if (!bad_range && count > 0 && total < first + count && total + chunk_len > first) {
-            const int64_t a = first > total ? first : total;
-            const int64_t b = first + count < total + chunk_len ? first + count : total + chunk_len;
-            part.lo = a - total;
-            part.count = b - a;
-            part.out_at = a - first;
-            parts.push_back(std::move(part));
-        }
-        total += chunk_len;
-        at = end_max;
-        if (size_known && total >= first + count) break;  // the range is covered
-        if (eof) break;
-    }
-    if (!size_known) {
-        if (file_len) *file_len = total;
-        if (bad_range || first > total || count > total - first) return MRZ_E_ARG;
-    } else if (total < first + count)
-        return MRZ_E_CORRUPT;  // fewer bytes than the header promised
-    if (!count) return MRZ_OK;
-    if (!out_host) return MRZ_E_ARG;
-
-    mrz_ctx *ctx = nullptr;
-    rc = mrz_open(&ctx, device, 7, 0);
-    std::vector<int64_t> origins;
-    for (size_t k = 0; !rc && k < parts.size(); k++) {
-        const RangePart &pt = parts[k];
-        origins.resize((size_t)pt.count);
-        mrz_range_info info;
-        rc = mrz_runzip_origins(ctx, pt.s0.data(), (int64_t)pt.s0.size(), pt.s1_len, MRZ_MEM_HOST, pt.cb, pt.lo, pt.count,
-                                origins.data(), MRZ_MEM_HOST, &info);
-        if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // the device's reading of the records differs from the host walk's
-        if (rc) break;
-        uint8_t *dst = (uint8_t *)out_host + pt.out_at;
-        for (int64_t i = 0; i < pt.count;) {  // runs of consecutive origins
-            int64_t j = i + 1;
-            while (j < pt.count && origins[(size_t)j] == origins[(size_t)j - 1] + 1) j++;
-            copy_from_blocks(pt.s1, origins[(size_t)i], j - i, dst + i);
-            i = j;
-        }
-    }
-    if (ctx) mrz_close(ctx);
-    return rc;
-}
-
-extern "C" int mrz_runzip_buffer_range(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count,
-                                       void *out_host, int64_t *file_len) {
-    try {
-        return runzip_buffer_range_impl(device, mrz_v, n, first, count, out_host, file_len);
-    } catch (const std::bad_alloc &) {
-        return MRZ_E_NOMEM;
-    } catch (const std::length_error &) {
-        return MRZ_E_CORRUPT;
-    }
-}
-
-// ---- ... and of a -l archive: stream 1 stays in its blocks, the touched ones are decoded as far as they are needed -----
-namespace {
-
-struct DeviceBuf {
-    uint8_t *p = nullptr;
-    ~DeviceBuf() {
-        if (p) hipFree(p);
-    }
-};
-
-struct CtxGuard {
-    mrz_ctx *ctx = nullptr;
-    ~CtxGuard() {
-        if (ctx) mrz_close(ctx);
-    }
-};
-
-// One entry of a chunk's stream-1 table: a block, or a piece of at most kLz4MaxInput bytes of a longer CTYPE_NONE
-// block, so that offsets inside an entry fit the 32 bits of mrz_uz_span.
-struct S1Piece {
-    size_t block;  // index into the chunk's stream-1 blocks
-    int64_t at;    // where the piece begins in its block
-};
-
-void s1_table(const std::vector<ArcBlock> &s1, std::vector<int64_t> &starts, std::vector<S1Piece> &pieces) {
-    int64_t at = 0;
-    for (size_t k = 0; k < s1.size(); k++) {
-        int64_t off = 0;
-        do {
-            starts.push_back(at + off);
-            pieces.push_back(S1Piece{ k, off });
-            off += kLz4MaxInput;
-        } while (off < s1[k].u_len);
-        at += s1[k].u_len;
-    }
-}
-
-// Bytes [lo, lo + cnt) of one chunk into d_out (device memory): origins, spans, the touched blocks' prefixes, gather.
-int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, int where0, const std::vector<ArcBlock> &s1,
-                       int64_t s1_len, int cb, int64_t lo, int64_t cnt, uint8_t *d_out, mrz_archive_range_info &acc) {
-    std::vector<int64_t> starts;
-    std::vector<S1Piece> pieces;
-    s1_table(s1, starts, pieces);
-    const int64_t nt = (int64_t)starts.size();
-    auto al = [](int64_t v) { return (v + 255) & ~255ll; };
-    const int64_t o_starts = al(cnt * 8), o_span = o_starts + al(nt * 8), o_base = o_span + al(nt * 8);
-    DeviceBuf tab;
-    if (hipMalloc((void **)&tab.p, (size_t)(o_base + al(nt * 8))) != hipSuccess) return MRZ_E_NOMEM;
-    int64_t *d_org = (int64_t *)tab.p, *d_starts = (int64_t *)(tab.p + o_starts), *d_base = (int64_t *)(tab.p + o_base);
-    mrz_uz_span *d_span = (mrz_uz_span *)(tab.p + o_span);
-
-    mrz_range_info ri;
-    int rc = mrz_runzip_origins(ctx, s0, s0_len, s1_len, where0, cb, lo, cnt, d_org, MRZ_MEM_DEVICE, &ri);
-    if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // the device's reading of the records differs from the length walk's
-    if (rc) return rc;
-    acc.chunks_in_range++;
-    acc.total_hops += ri.total_hops;
-    if (ri.max_hops > acc.max_hops) acc.max_hops = ri.max_hops;
-
-    std::vector<mrz_uz_span> span((size_t)nt, mrz_uz_span{ 0xffffffffu, 0u });
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d_starts, starts.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_span, span.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, mrz_launch_block_span(s, cus, d_org, cnt, d_starts, nt, d_span));
-    HIPCHK(ctx, hipMemcpyAsync(span.data(), d_span, (size_t)nt * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-
-    // what the touched entries need: LZ4 payloads in front, then per entry the bytes from its lowest offset on
-    int64_t packed = 0, staged = 0;
-    for (int64_t t = 0; t < nt; t++) {
-        if (span[(size_t)t].lo > span[(size_t)t].hi) continue;
-        const ArcBlock &b = s1[pieces[(size_t)t].block];
-        const int64_t hi = span[(size_t)t].hi, low = span[(size_t)t].lo;
-        if (pieces[(size_t)t].at + hi >= b.u_len) return MRZ_E_STATE;  // (an origin lies below s1_len: cannot happen)
-        if (b.ctype == kCtypeLz4) {
-            packed += (b.c_len + 31) & ~15ll;
-            staged += (hi + 1 + 31) & ~15ll;
-        } else
-            staged += (hi - low + 1 + 31) & ~15ll;
-    }
-    DeviceBuf stage;
-    if (hipMalloc((void **)&stage.p, (size_t)(packed + staged + 64)) != hipSuccess) return MRZ_E_NOMEM;
-    std::vector<int64_t> base((size_t)nt, 0);
-    std::vector<const void *> src;
-    std::vector<void *> dst;
-    std::vector<int64_t> c_lens, u_lens, wants;
-    int64_t pk = 0, st = packed;
-    size_t last_block = (size_t)-1;
-    for (int64_t t = 0; t < nt; t++) {
-        if (span[(size_t)t].lo > span[(size_t)t].hi) continue;
-        const S1Piece &pc = pieces[(size_t)t];
-        const ArcBlock &b = s1[pc.block];
-        const int64_t hi = span[(size_t)t].hi, low = span[(size_t)t].lo;
-        if (pc.block != last_block) acc.s1_blocks_touched++;
-        last_block = pc.block;
-        if (b.ctype == kCtypeLz4) {  // the prefix [0, hi]: a decode cannot begin anywhere else
-            if (b.c_len) HIPCHK(ctx, hipMemcpyAsync(stage.p + pk, b.p, (size_t)b.c_len, hipMemcpyHostToDevice, s));
-            src.push_back(stage.p + pk);
-            dst.push_back(stage.p + st);
-            c_lens.push_back(b.c_len);
-            u_lens.push_back(b.u_len);
-            wants.push_back(hi + 1);
-            base[(size_t)t] = st + low;
-            pk += (b.c_len + 31) & ~15ll;
-            st += (hi + 1 + 31) & ~15ll;
-            acc.s1_lz4_bytes += hi + 1;
-            acc.s1_bytes_uploaded += b.c_len;
-        } else {  // bytes [low, hi] of the piece
-            HIPCHK(ctx, hipMemcpyAsync(stage.p + st, b.p + pc.at + low, (size_t)(hi - low + 1), hipMemcpyHostToDevice, s));
-            base[(size_t)t] = st;
-            st += (hi - low + 1 + 31) & ~15ll;
-            acc.s1_bytes_uploaded += hi - low + 1;
-        }
-    }
-    if (src.size() > 0x7fffffffu) return MRZ_E_UNSUPPORTED;
-    HIPCHK(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if (!src.empty()) {
-        std::vector<int32_t> status(src.size());
-        rc = mrz_lz4_decompress_prefix_batch(ctx, src.data(), c_lens.data(), (int)src.size(), MRZ_MEM_DEVICE, dst.data(),
-                                             u_lens.data(), wants.data(), MRZ_MEM_DEVICE, status.data());
-        if (rc) return rc;
-        for (int32_t v : status)
-            if (v) return MRZ_E_CORRUPT;
-    }
-    HIPCHK(ctx, mrz_launch_block_gather(s, cus, d_org, cnt, d_starts, nt, d_span, d_base, stage.p, d_out));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return MRZ_OK;
-}
-
-}  // namespace
-
-static int runzip_buffer_range_ex_impl(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out,
-                                       int out_where, int64_t *file_len, mrz_archive_range_info &acc) {
-    if (!mrz_v || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE)) return MRZ_E_ARG;
-    const uint8_t *mrz = (const uint8_t *)mrz_v;
-    int64_t expected = 0;
-    int hash_code = 0;
-    int rc = read_archive_header(mrz, n, &expected, &hash_code);
-    if (rc) return rc;
-    const bool size_known = expected > 0;
-    if (size_known) {
-        if (file_len) *file_len = expected;
-        if (first < 0 || count < 0 || first > expected || count > expected - first) return MRZ_E_ARG;
-        if (!count) return MRZ_OK;
-        if (!out) return MRZ_E_ARG;
-    }
-    // without a size the file's length is still owed to a caller whose range is wrong: the walk goes on, the work does not
-    const bool bad_range = first < 0 || count < 0 || count > INT64_MAX - first || (count > 0 && !out);
-    CtxGuard g;
-    int cus = 0;
-    auto open_ctx = [&]() {  // on first need: an archive may be walked without any device work
-        if (g.ctx) return (int)MRZ_OK;
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        return mrz_open(&g.ctx, device, 7, 0);
-    };
-    DeviceBuf scratch;  // the range, when `out` is host memory
-    uint8_t *d_out = out_where == MRZ_MEM_DEVICE ? (uint8_t *)out : nullptr;
-    int64_t at = 20 + mrz[19], total = 0;
-    std::vector<uint8_t> s0;
-    for (;;) {
-        if (at + 2 > n) return MRZ_E_CORRUPT;
-        const int cb = mrz[at], eof = mrz[at + 1];
-        if (cb < 1 || cb > 8 || at + 2 + cb > n) return MRZ_E_CORRUPT;
-        at += 2 + cb;
-        const int64_t initial_pos = at;
-        int64_t end_max = initial_pos + 2 * (1 + 3 * cb);
-        std::vector<ArcBlock> blocks[2];
-        int64_t stream_len[2] = { 0, 0 };
-        rc = list_stream(mrz, n, initial_pos, initial_pos, cb, blocks[0], &stream_len[0], &end_max);
-        if (!rc) rc = list_stream(mrz, n, initial_pos, initial_pos + 1 + 3 * cb, cb, blocks[1], &stream_len[1], &end_max);
-        if (rc) return rc;
-        int64_t s0_lz4 = 0;
-        for (const ArcBlock &b : blocks[0])
-            if (b.ctype == kCtypeLz4) s0_lz4 += b.u_len;
-        const bool s0_on_device = s0_lz4 > 0;
-        // stream 0 and the chunk's length: on the device where it holds an LZ4 block (decoded whole: the parse needs
-        // every record), otherwise gathered and walked on the host as mrz_runzip_buffer_range does
-        DeviceStreams ds;
-        int64_t chunk_len = 0;
-        s0.clear();
-        if (s0_on_device) {
-            if (blocks[0].size() > 0x7fffffffu) return MRZ_E_UNSUPPORTED;
-            rc = open_ctx();
-            if (rc) return rc;
-            const std::vector<ArcBlock> only0[2] = { blocks[0], std::vector<ArcBlock>() };
-            const int64_t len0[2] = { stream_len[0], 0 };
-            rc = build_device_streams(g.ctx, only0, len0, ds);
-            if (rc) return rc;
-            acc.s0_lz4_bytes += s0_lz4;
-            mrz_range_info ri;
-            rc = mrz_runzip_origins(g.ctx, ds.s0, stream_len[0], stream_len[1], MRZ_MEM_DEVICE, cb, 0, 0, nullptr,
-                                    MRZ_MEM_DEVICE, &ri);
-            if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // too short to hold a terminator
-            if (rc) return rc;
-            chunk_len = ri.chunk_len;
-        } else {
-            for (const ArcBlock &b : blocks[0]) s0.insert(s0.end(), b.p, b.p + b.c_len);
-            if (!records_out_len(s0, cb, &chunk_len)) return MRZ_E_CORRUPT;
-        }
-        if (!bad_range && count > 0 && total < first + count && total + chunk_len > first) {
-            const int64_t a = first > total ? first : total;
-            const int64_t b = first + count < total + chunk_len ? first + count : total + chunk_len;
-            rc = open_ctx();
-            if (rc) return rc;
-            if (!d_out) {
-                if (hipMalloc((void **)&scratch.p, (size_t)count) != hipSuccess) return MRZ_E_NOMEM;
-                d_out = scratch.p;
-            }
-            rc = range_chunk_blocks(g.ctx, cus, s0_on_device ? (const void *)ds.s0 : (const void *)s0.data(),
-                                    s0_on_device ? stream_len[0] : (int64_t)s0.size(),
-                                    s0_on_device ? MRZ_MEM_DEVICE : MRZ_MEM_HOST, blocks[1], stream_len[1], cb, a - total,
-                                    b - a, d_out + (a - first), acc);
-            if (rc) return rc;
-        }
-        total += chunk_len;
-        at = end_max;
-        if (size_known && total >= first + count) break;  // the range is covered
-        if (eof) break;
-    }
-    if (!size_known) {
-        if (file_len) *file_len = total;
-        if (first < 0 || count < 0 || first > total || count > total - first) return MRZ_E_ARG;
-    } else if (total < first + count)
-        return MRZ_E_CORRUPT;  // fewer bytes than the header promised
-    if (!count) return MRZ_OK;
-    if (!out) return MRZ_E_ARG;
-    if (scratch.p && hipMemcpy(out, scratch.p, (size_t)count, hipMemcpyDeviceToHost) != hipSuccess) return MRZ_E_HIP;
-    return MRZ_OK;
-}
-
-extern "C" int mrz_runzip_buffer_range_ex(int device, const void *mrz_v, int64_t n, int64_t first, int64_t count, void *out,
-                                          int out_where, int64_t *file_len, mrz_archive_range_info *info) {
-    mrz_archive_range_info acc;
-    memset(&acc, 0, sizeof(acc));
-    int rc;
-    try {
-        rc = runzip_buffer_range_ex_impl(device, mrz_v, n, first, count, out, out_where, file_len, acc);
-    } catch (const std::bad_alloc &) {
-        rc = MRZ_E_NOMEM;
-    } catch (const std::length_error &) {
-        rc = MRZ_E_CORRUPT;
-    }
-    if (info) *info = acc;
-    return rc;
 }
