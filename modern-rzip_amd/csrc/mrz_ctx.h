@@ -101,6 +101,12 @@ struct mrz_ctx {
     void *cand_user;
 };
 
+// a context of the host driver's own (mrz_host.hip, mrz_unarchive.hip), closed when the scope is left
+struct CtxGuard {
+    mrz_ctx *ctx = nullptr;
+    ~CtxGuard() { mrz_close(ctx); }
+};
+
 #define HIPCHK(ctx, expr)                     \
     do {                                      \
         hipError_t e__ = (expr);              \

@@ -1,5 +1,5 @@
 // mrz_md5.h -- MD5 (RFC 1321; libgcrypt GCRY_MD_MD5 in the reference): the whole-file hash of a -n archive, written by
-// mrz_host.hip and checked by mrz_unarchive.hip.  Host code.
+// mrz_host.hip (through mrz_framing.h's sink) and checked by mrz_unarchive.hip.  Host code.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

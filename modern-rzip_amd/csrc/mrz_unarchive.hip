@@ -25,11 +25,6 @@ struct DeviceBuf {
     }
 };
 
-struct CtxGuard {
-    mrz_ctx *ctx = nullptr;
-    ~CtxGuard() { mrz_close(ctx); }
-};
-
 // Streams of a chunk that holds LZ4 blocks, put together in device memory: CTYPE_NONE payloads are copied into place,
 // LZ4 payloads are uploaded as they are and decoded into place by mrz_lz4_decompress_batch, all blocks of all streams
 // in one launch.  What the blocks decode to never exists in host memory.
