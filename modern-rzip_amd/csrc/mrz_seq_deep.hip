@@ -22,7 +22,10 @@
 //           MRZ_DEEP_GROUP instructions in flight: first empty slot, the tag-equal entries in probe order (and a 64-byte
 //           probe of each, single_match_len :372-397), where insert_hash's walk stops (:264-297: empty / due for culling /
 //           lower-ranked occupant to displace / the max_chain_len-th tag-equal entry => eviction) and where the displaced
-//           occupant's own walk stops.  Read-only, against the table as it stands;
+//           occupant's own walk stops.  Read-only, against the table as it stands.  The next group's loads are issued
+//           before the current group is folded, and a group in which no lane sees anything that could change the walk's
+//           state is passed with one ballot (mrz_deep_scan; profiles/scanwalk: the walk is bound by the wave's VALU
+//           issue, 5 us of folding against 0.9 us of waiting for loads per run at 13 bits; tar-64G 9.45 -> 9.07 s);
 //   COMMIT  wave 0 replays the lanes in position order.  A lane commits as scanned unless an earlier lane of the batch
 //           has changed what its scan DEPENDS ON -- which is little (mrz_deep_stale): the slot it writes, the slot its
 //           occupant moves to, its first empty slot, an entry with its tag or its occupant's tag written, moved or
@@ -268,16 +271,81 @@ static_assert(MRZ_DEEP_CW_WORDS == 32, "mrz_deep_cw_slot searches 32 words in 5 
 // walk found before that position stands (the precise dependency rule: no other write there matters), so the run is
 // taken up again AT that slot instead of being read from its start -- one or two loads instead of 20-170 at masks of 11+
 // bits, where most conflicts are several inserters of one run wanting the same slot.
+// The table as the scan reads it: a pointer that carries the global address space, so that the walk's loads are
+// global_load_dwordx4 -- they return in order, which is what lets a wait leave the next group's loads outstanding
+// (flat loads may return out of order and tie lgkmcnt into every wait: with them reading ahead hides nothing).
+// The base is wave-uniform (scalar registers) and a slot is addressed by its BYTE offset, 32 bits per lane: a table is
+// at most 64 MiB (the levels of mrz_capi.hip), so two VALU instructions make a load's address.
+// -DMRZ_DEEP_SCAN_FLAT keeps the generic pointer (measurements only).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MRZ_DEEP_SCAN_FLAT)
+typedef long long mrz_deep_v2l __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) char *mrz_deep_tab;
+__device__ __forceinline__ mrz_deep_tab mrz_deep_tab_of(const mrz_slot *tab) {
+    return (mrz_deep_tab)(uintptr_t)mrz_uni64((int64_t)(uintptr_t)tab);
+}
+__device__ __forceinline__ mrz_slot mrz_deep_tab_ld(mrz_deep_tab tab, unsigned byte_off) {
+    const mrz_deep_v2l v = *(const __attribute__((address_space(1))) mrz_deep_v2l *)(tab + byte_off);
+    mrz_slot e;
+    e.off = v.x;
+    e.t = v.y;
+    return e;
+}
+#else
+typedef const mrz_slot *mrz_deep_tab;
+__device__ __forceinline__ mrz_deep_tab mrz_deep_tab_of(const mrz_slot *tab) { return tab; }
+__device__ __forceinline__ mrz_slot mrz_deep_tab_ld(mrz_deep_tab tab, unsigned byte_off) { return tab[byte_off >> 4]; }
+#endif
+// the split of ONE wave's walk (-DMRZ_SEQ_PROFILE, the caller that passes `wprof`: helper 0's wave 0): [0] cycles from
+// issuing a group's loads to the end of the wait in front of its fold, [1] cycles folding (or passing) the group.  The
+// wait is spelled out here so that it falls on this side of the timer; `n` loads (the next group's) stay outstanding.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MRZ_DEEP_SCAN_VECTOR_STATE)  // (that switch: measurements only)
+#define MRZ_DEEP_UNI(v) mrz_uni(v)
+#define MRZ_DEEP_UNI64(v) mrz_uni64(v)
+#else
+#define MRZ_DEEP_UNI(v) (v)
+#define MRZ_DEEP_UNI64(v) (v)
+#endif
+#ifdef __HIP_DEVICE_COMPILE__
+#define MRZ_DEEP_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define MRZ_DEEP_SCHED_FENCE() ((void)0)
+#endif
+#ifdef MRZ_SEQ_PROFILE
+#define MRZ_DSCAN_PROF_PARAM , int64_t *wprof = nullptr
+#define DSCAN_T0() int64_t dscan_t0 = wprof ? (int64_t)__builtin_amdgcn_s_memtime() : 0
+#define DSCAN_WAIT(n) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(n) : "memory")
+#define DSCAN_ADD(k)                                                     \
+    do {                                                                 \
+        if (wprof) {                                                     \
+            const int64_t now__ = (int64_t)__builtin_amdgcn_s_memtime(); \
+            wprof[k] += now__ - dscan_t0;                                \
+            dscan_t0 = now__;                                            \
+        }                                                                \
+    } while (0)
+#else
+#define MRZ_DSCAN_PROF_PARAM
+#define DSCAN_T0()
+#define DSCAN_WAIT(n)
+#define DSCAN_ADD(k)
+#endif
 __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, int64_t better, int64_t tag_mask,
-                                     int64_t clean_ptr, int xw_n, int lane, int from = 0) {
-    const mrz_slot *tab = C.tab;
+                                     int64_t clean_ptr, int xw_n, int lane, int from = 0 MRZ_DSCAN_PROF_PARAM) {
+    // (the arguments of a function that is not inlined arrive in vector registers: said to be wave-uniform here, the
+    // walk's state -- kind, round, alt_st, fe ... -- is the wave's scalars and the loop's branches are scalar branches)
+    i = MRZ_DEEP_UNI(i);
+    from = MRZ_DEEP_UNI(from);
+    xw_n = MRZ_DEEP_UNI(xw_n);
+    better = MRZ_DEEP_UNI64(better);
+    tag_mask = MRZ_DEEP_UNI64(tag_mask);
+    clean_ptr = MRZ_DEEP_UNI64(clean_ptr);
+    const mrz_deep_tab tab = mrz_deep_tab_of(C.tab);
     const uint8_t *__restrict__ buf = C.buf;
-    const int smask = (int)C.slot_mask;
-    const int max_chain = (int)C.max_chain;
+    const int smask = MRZ_DEEP_UNI((int)C.slot_mask);
+    const int max_chain = MRZ_DEEP_UNI((int)C.max_chain);
     const int64_t q = mrz_uni64(S->R.q[i]), t = mrz_uni64(S->R.t[i]);
     const bool ins = (t & tag_mask) == tag_mask;
     const int my_rank = mrz_ones_rank(t);
-    const int h = (int)(t & C.slot_mask);
+    const int h = (int)(t & (int64_t)smask);
     int fe = -1, w = -1, kind = ins ? -1 : MRZ_DK_NONE;
     int nsame = 0, round = 0;
     bool cplx = false;
@@ -307,104 +375,174 @@ __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, i
         }
     }
     const int start = cont ? from : 0;
-    const int max_groups = (int)((C.nslots + 64 * MRZ_DEEP_GROUP - 1) / (64 * MRZ_DEEP_GROUP)) + 1;
-    for (int grp = 0; fe < 0; grp++) {
+    const int max_groups = (int)(((int64_t)smask + 1 + 64 * MRZ_DEEP_GROUP - 1) / (64 * MRZ_DEEP_GROUP)) + 1;
+    // The walk, a group of MRZ_DEEP_GROUP blocks at a time, in two sets of registers: the loads of group g + 1 are issued
+    // before group g is folded, so the fold runs under the next group's memory latency.  A group read beyond the run's end
+    // costs nothing but its loads: addresses are masked into the table, the table is not written while a batch is
+    // scanned, and what is still outstanding when the walk ends is dropped.  No branch stands between the loads and the
+    // fold: a wait behind a join is the strictest of its paths' waits, and one path that does not read ahead (tried: a
+    // continuation's first group) made the compiler wait for the loads just issued on every path.
+    // (-DMRZ_DEEP_SCAN_NO_AHEAD: every group is loaded when its turn has come, as before.)
+    mrz_slot e2[2][MRZ_DEEP_GROUP];
+    const int sl = h + start + lane;
+    // (the byte offsets of the NEXT group to load are kept in registers of their own and moved on BEHIND the loads: made
+    // in front of them, the sums went through a temporary that was given a register of the set about to be loaded, and
+    // the compiler put a vmcnt(0) before it)
+    const unsigned bmask = (unsigned)smask << 4;
+    unsigned bo[MRZ_DEEP_GROUP];
+#pragma unroll
+    for (int g = 0; g < MRZ_DEEP_GROUP; g++) bo[g] = (((unsigned)sl << 4) + (unsigned)g * 1024u) & bmask;
+#define MRZ_DEEP_LOAD_NEXT_GROUP(set)                                                                          \
+    _Pragma("unroll") for (int g = 0; g < MRZ_DEEP_GROUP; g++) e2[set][g] = mrz_deep_tab_ld(tab, bo[g]);       \
+    MRZ_DEEP_SCHED_FENCE();                                                                                    \
+    _Pragma("unroll") for (int g = 0; g < MRZ_DEEP_GROUP; g++) bo[g] = (bo[g] + MRZ_DEEP_GROUP * 1024u) & bmask
+#ifndef MRZ_DEEP_SCAN_NO_AHEAD
+    MRZ_DEEP_LOAD_NEXT_GROUP(0);
+#endif
+#ifndef MRZ_DEEP_SCAN_NO_QUIET
+    // an entry is due for culling or lower-ranked than t exactly if it lacks one of these bits (or is all ones, which
+    // mrz_ones_rank ranks lowest)
+    const int64_t stop_bits = better | (int64_t)(my_rank > 0 ? mrz_low_mask(my_rank - 1) : 0ull);
+#endif
+    for (int grp = 0; fe < 0; grp += 2) {
         if (grp >= max_groups) {  // cannot happen: the table is at most 2/3 full
             cplx = true;
             fe = h;
             break;
         }
-        mrz_slot e[MRZ_DEEP_GROUP];
-        const int s0 = h + start + grp * (64 * MRZ_DEEP_GROUP) + lane;
 #pragma unroll
-        for (int g = 0; g < MRZ_DEEP_GROUP; g++) e[g] = tab[(s0 + g * 64) & smask];
-#pragma unroll
-        for (int g = 0; g < MRZ_DEEP_GROUP; g++) {
+        for (int half = 0; half < 2; half++) {
             if (fe >= 0) continue;
-            const int sb = s0 - lane + g * 64;  // slot of lane 0 (before masking)
-            const bool empty = (e[g].off | e[g].t) == 0;
-            const mrz_u64 m_empty = __ballot(empty);
-            const int fe_idx = m_empty ? __ffsll((long long)m_empty) - 1 : 64;
-            const mrz_u64 valid = mrz_low_mask(fe_idx);
-            const mrz_u64 m_same = __ballot(!empty && e[g].t == t) & valid;
-            mrz_u64 m_due = 0, m_low = 0;
-            if (kind == -1 || alt_st == 1) {
-                m_due = __ballot(!empty && (e[g].t & better) != better) & valid;
-                m_low = __ballot(!empty && mrz_ones_rank(e[g].t) < my_rank) & valid & ~m_due;
+            const int gi = grp + half;
+            DSCAN_T0();
+#ifdef MRZ_DEEP_SCAN_NO_AHEAD
+            MRZ_DEEP_LOAD_NEXT_GROUP(half);
+            DSCAN_WAIT(0);
+#else
+            MRZ_DEEP_LOAD_NEXT_GROUP(half ^ 1);
+            MRZ_DEEP_SCHED_FENCE();  // (the scheduler had moved the first tests of this group's entries, and their waits, above the loads)
+            DSCAN_WAIT(MRZ_DEEP_GROUP);
+#endif
+            DSCAN_ADD(0);
+            const mrz_slot(&e)[MRZ_DEEP_GROUP] = e2[half];
+            const int s0 = h + start + gi * (64 * MRZ_DEEP_GROUP);  // slot of lane 0 in the group's first block (before masking)
+#ifndef MRZ_DEEP_SCAN_NO_QUIET
+            // A QUIET group is passed with one ballot.  Invariant: if no lane holds, in any block of the group, an empty
+            // slot or an entry with tag t -- nor, while the insert's place or the alternative stop is still open, an entry
+            // that is due or lower-ranked --, then every block below has fe_idx == 64, m_same == 0 and, where they are
+            // looked at, m_due == m_low == 0, so ks == ks2 == 64 and nq == nq2 == 0: the block code stores nothing and
+            // changes no state, EXCEPT that an open walk whose count of passed tag-equal entries has reached max_chain
+            // (a continuation may start there) turns into an eviction -- such a group is not skipped.  `open` cannot become
+            // true inside a group that it was false at the start of (kind leaves -1 for good; alt_st becomes 1 only where
+            // kind was -1), so testing it once per group is enough.
+            // (The test is spelled with the block code's own expressions, which the compiler then shares with a loud group's
+            // blocks.  A version that looked at the tags' low words only -- fewer and cheaper compares, but none shared --
+            // was slower: 4.7 against 3.9 us of folding per walk, tar-64G 9.28 against 9.07 s.)
+            {
+                const bool open = kind == -1 || alt_st == 1;
+                bool loud = false;
+#pragma unroll
+                for (int g = 0; g < MRZ_DEEP_GROUP; g++) {
+                    const int64_t et = e[g].t;
+                    loud |= ((e[g].off | et) == 0) | (et == t);
+                    if (open) loud |= ((et & stop_bits) != stop_bits) | (et == -1);
+                }
+                if (__ballot(loud) == 0 && (kind != -1 || round < max_chain) && (alt_st != 1 || alt_round < max_chain)) {
+                    DSCAN_ADD(1);
+                    continue;
+                }
             }
-            int alt_from = 0;  // first slot of this block the search for the next stop looks at
-            if (kind == -1) {
-                const mrz_u64 m_stop = m_due | m_low;
-                const int ks = m_stop ? __ffsll((long long)m_stop) - 1 : 64;
-                const int nq = __popcll(m_same & mrz_low_mask(ks));
-                if (round + nq >= max_chain) {
-                    kind = MRZ_DK_EVICT;  // the victim is the victim_round-th tag-equal entry: picked at the commit
-                } else {
-                    round += nq;
-                    if (ks < 64) {
-                        w = (sb + ks) & smask;
-                        if ((m_due >> ks) & 1) {
-                            kind = MRZ_DK_OVER;
-                            old_t = mrz_bcast64(e[g].t, ks);
-                            alt_st = 1;
-                            alt_from = ks + 1;
-                            alt_round = round;
-                        } else {
-                            kind = MRZ_DK_DISPLACE;
-                            occ_t = mrz_bcast64(e[g].t, ks);
-                            occ_off = mrz_bcast64(e[g].off, ks);
+#endif
+#pragma unroll
+            for (int g = 0; g < MRZ_DEEP_GROUP; g++) {
+                if (fe >= 0) continue;
+                const int sb = s0 + g * 64;  // slot of lane 0 (before masking)
+                const bool empty = (e[g].off | e[g].t) == 0;
+                const mrz_u64 m_empty = __ballot(empty);
+                const int fe_idx = m_empty ? __ffsll((long long)m_empty) - 1 : 64;
+                const mrz_u64 valid = mrz_low_mask(fe_idx);
+                const mrz_u64 m_same = __ballot(!empty && e[g].t == t) & valid;
+                mrz_u64 m_due = 0, m_low = 0;
+                if (kind == -1 || alt_st == 1) {
+                    m_due = __ballot(!empty && (e[g].t & better) != better) & valid;
+                    m_low = __ballot(!empty && mrz_ones_rank(e[g].t) < my_rank) & valid & ~m_due;
+                }
+                int alt_from = 0;  // first slot of this block the search for the next stop looks at
+                if (kind == -1) {
+                    const mrz_u64 m_stop = m_due | m_low;
+                    const int ks = m_stop ? __ffsll((long long)m_stop) - 1 : 64;
+                    const int nq = __popcll(m_same & mrz_low_mask(ks));
+                    if (round + nq >= max_chain) {
+                        kind = MRZ_DK_EVICT;  // the victim is the victim_round-th tag-equal entry: picked at the commit
+                    } else {
+                        round += nq;
+                        if (ks < 64) {
+                            w = (sb + ks) & smask;
+                            if ((m_due >> ks) & 1) {
+                                kind = MRZ_DK_OVER;
+                                old_t = mrz_bcast64(e[g].t, ks);
+                                alt_st = 1;
+                                alt_from = ks + 1;
+                                alt_round = round;
+                            } else {
+                                kind = MRZ_DK_DISPLACE;
+                                occ_t = mrz_bcast64(e[g].t, ks);
+                                occ_off = mrz_bcast64(e[g].off, ks);
+                            }
+                        } else if (fe_idx < 64) {
+                            w = (sb + fe_idx) & smask;
+                            kind = MRZ_DK_EMPTY;
+                            // (behind a first empty slot that somebody else fills: the slot after it, if that is empty too)
+                            if (fe_idx < 63 && ((m_empty >> (fe_idx + 1)) & 1)) {
+                                alt_w = (sb + fe_idx + 1) & smask;
+                                alt_kind = MRZ_DK_EMPTY;
+                            }
+                            alt_st = 2;
                         }
-                    } else if (fe_idx < 64) {
-                        w = (sb + fe_idx) & smask;
-                        kind = MRZ_DK_EMPTY;
-                        // (behind a first empty slot that somebody else fills: the slot after it, if that is empty too)
-                        if (fe_idx < 63 && ((m_empty >> (fe_idx + 1)) & 1)) {
-                            alt_w = (sb + fe_idx + 1) & smask;
+                    }
+                }
+                if (alt_st == 1 && alt_from < 64) {
+                    const mrz_u64 beyond = ~mrz_low_mask(alt_from);
+                    const mrz_u64 m_stop2 = (m_due | m_low) & beyond;
+                    const int ks2 = m_stop2 ? __ffsll((long long)m_stop2) - 1 : 64;
+                    const int nq2 = __popcll(m_same & beyond & mrz_low_mask(ks2));
+                    if (alt_round + nq2 >= max_chain)
+                        alt_st = 2;  // (the chain limit comes first: an eviction, not a plain stop)
+                    else {
+                        alt_round += nq2;
+                        if (ks2 < 64) {
+                            if ((m_due >> ks2) & 1) {
+                                alt_w = (sb + ks2) & smask;
+                                alt_kind = MRZ_DK_OVER;
+                                alt_old_t = mrz_bcast64(e[g].t, ks2);
+                            }
+                            alt_st = 2;  // (a lower-ranked occupant: a displacement, not recorded)
+                        } else if (fe_idx < 64) {
+                            alt_w = (sb + fe_idx) & smask;
                             alt_kind = MRZ_DK_EMPTY;
+                            alt_st = 2;
                         }
-                        alt_st = 2;
                     }
                 }
-            }
-            if (alt_st == 1 && alt_from < 64) {
-                const mrz_u64 beyond = ~mrz_low_mask(alt_from);
-                const mrz_u64 m_stop2 = (m_due | m_low) & beyond;
-                const int ks2 = m_stop2 ? __ffsll((long long)m_stop2) - 1 : 64;
-                const int nq2 = __popcll(m_same & beyond & mrz_low_mask(ks2));
-                if (alt_round + nq2 >= max_chain)
-                    alt_st = 2;  // (the chain limit comes first: an eviction, not a plain stop)
-                else {
-                    alt_round += nq2;
-                    if (ks2 < 64) {
-                        if ((m_due >> ks2) & 1) {
-                            alt_w = (sb + ks2) & smask;
-                            alt_kind = MRZ_DK_OVER;
-                            alt_old_t = mrz_bcast64(e[g].t, ks2);
+                if (m_same) {
+                    if ((m_same >> lane) & 1) {
+                        const int k = nsame + __popcll(m_same & mrz_low_mask(lane));
+                        if (k < MRZ_SMAX) {
+                            S->R.same_slot[i][k] = (sb + lane) & smask;
+                            S->R.same_off[i][k] = e[g].off;
                         }
-                        alt_st = 2;  // (a lower-ranked occupant: a displacement, not recorded)
-                    } else if (fe_idx < 64) {
-                        alt_w = (sb + fe_idx) & smask;
-                        alt_kind = MRZ_DK_EMPTY;
-                        alt_st = 2;
                     }
+                    nsame += __popcll(m_same);
+                }
+                if (fe_idx < 64) {
+                    fe = (sb + fe_idx) & smask;
+                    fe2 = fe_idx < 63 && ((m_empty >> (fe_idx + 1)) & 1);
                 }
             }
-            if (m_same) {
-                if ((m_same >> lane) & 1) {
-                    const int k = nsame + __popcll(m_same & mrz_low_mask(lane));
-                    if (k < MRZ_SMAX) {
-                        S->R.same_slot[i][k] = (sb + lane) & smask;
-                        S->R.same_off[i][k] = e[g].off;
-                    }
-                }
-                nsame += __popcll(m_same);
-            }
-            if (fe_idx < 64) {
-                fe = (sb + fe_idx) & smask;
-                fe2 = fe_idx < 63 && ((m_empty >> (fe_idx + 1)) & 1);
-            }
+            DSCAN_ADD(1);
         }
     }
+#undef MRZ_DEEP_LOAD_NEXT_GROUP
     if (nsame > MRZ_SMAX) cplx = true;
     if (kind == MRZ_DK_EVICT && max_chain > MRZ_SMAX) cplx = true;
     // the displaced occupant's own walk (src/rzip.c:275-278; the table still holds it at `w`)
@@ -412,7 +550,7 @@ __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, i
     int64_t old_t2 = 0;
     if (kind == MRZ_DK_DISPLACE && !cplx) {
         const int rank2 = mrz_ones_rank(occ_t);
-        h2 = (int)(occ_t & C.slot_mask);
+        h2 = (int)(occ_t & (int64_t)smask);
         int round2 = 0;
         bool done = false;
         for (int grp = 0; !done; grp++) {
@@ -423,7 +561,7 @@ __device__ static void mrz_deep_scan(const mrz_cfg &C, mrz_deep_lds *S, int i, i
             mrz_slot e[MRZ_DEEP_GROUP];
             const int s0 = h2 + grp * (64 * MRZ_DEEP_GROUP) + lane;
 #pragma unroll
-            for (int g = 0; g < MRZ_DEEP_GROUP; g++) e[g] = tab[(s0 + g * 64) & smask];
+            for (int g = 0; g < MRZ_DEEP_GROUP; g++) e[g] = mrz_deep_tab_ld(tab, (unsigned)((s0 + g * 64) & smask) << 4);
 #pragma unroll
             for (int g = 0; g < MRZ_DEEP_GROUP; g++) {
                 if (done) continue;
@@ -752,7 +890,7 @@ __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, m
     unsigned long long seen = 0;
     int retries = 0;  // looks in a row at a job line whose stamp was not the number polled (wave-uniform)
 #ifdef MRZ_SEQ_PROFILE
-    int64_t hprof[4] = {0, 0, 0, 0};  // (ticket 0's thread 0 reports: MRZ_ST_DH_T_ACQ ...)
+    int64_t hprof[6] = {0, 0, 0, 0, 0, 0};  // (ticket 0's thread 0 reports: MRZ_ST_DH_T_ACQ ...; [4], [5]: the split of its wave's walks)
 #endif
     DPROF_T0();
     while (true) {
@@ -803,7 +941,11 @@ __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, m
             int k = 0;
             for (int i = me; i < nb; i += nscan, k++)
                 if (k % MRZ_DEEP_WAVES == wave) {
+#ifdef MRZ_SEQ_PROFILE
+                    mrz_deep_scan(C, S, i, better, tag_mask, clean_ptr, xw_n, lane, 0, ticket == 0 && wave == 0 ? &hprof[4] : nullptr);
+#else
                     mrz_deep_scan(C, S, i, better, tag_mask, clean_ptr, xw_n, lane);
+#endif
                     mrz_deep_rec_send(recmem, S, i, lane);
                 }
             mine_n = k;
@@ -826,7 +968,7 @@ __device__ static void mrz_deep_scan_helper(const mrz_cfg &C, mrz_deep_lds *S, m
 #ifdef MRZ_SEQ_PROFILE
     // (the committer leaves these four slots alone; one launch at a time runs on a context's state)
     if (tid == 0 && ticket == 0)
-        for (int k = 0; k < 4; k++) C.st->prof[MRZ_ST_DH_T_ACQ + k] += hprof[k];
+        for (int k = 0; k < 6; k++) C.st->prof[MRZ_ST_DH_T_ACQ + k] += hprof[k];
 #endif
 }
 
@@ -1667,7 +1809,7 @@ __global__ __launch_bounds__(MRZ_DEEP_THREADS) void mrz_seq_deep_kernel(mrz_seq_
         st->hint_matched = L.mbytes;
 #ifdef MRZ_SEQ_STATS
         for (int k = 0; k < MRZ_ST_N; k++)
-            if (k < MRZ_ST_DH_T_ACQ || k > MRZ_ST_DH_T_OUT) st->prof[k] += stat[k];  // (those: the scan helper with ticket 0)
+            if (k < MRZ_ST_DH_T_ACQ || k > MRZ_ST_DH_T_FOLD) st->prof[k] += stat[k];  // (those: the scan helper with ticket 0)
 #endif
     }
 }

@@ -35,9 +35,11 @@
     X(D_S_STALE, "d_s_stale") X(D_C_OVER_ALT, "d_c_over_alt") X(D_C_OVER_NOALT, "d_c_over_noalt") \
     X(D_C_EMPTY, "d_c_empty") X(D_C_DISPLACE, "d_c_displace") X(D_C_OTHER, "d_c_other") \
     /* (the split of d_t_scan -- committer: post the job, scan its own share, wait for the helpers, copy their records in; \
-       the scan helper with ticket 0: from the poll's match to the end of its acquire, read the job, scan, records out + signal) */ \
+       the scan helper with ticket 0: from the poll's match to the end of its acquire, read the job, scan, records out + signal; \
+       of its wave 0's walks: from issuing a group's loads to the end of the wait before its fold, and the folds) */ \
     X(D_T_POST, "d_t_post") X(D_T_OWN, "d_t_own") X(D_T_WAIT, "d_t_wait") X(D_T_COPYIN, "d_t_copyin") \
-    X(DH_T_ACQ, "dh_t_acq") X(DH_T_JOB, "dh_t_job") X(DH_T_SCAN, "dh_t_scan") X(DH_T_OUT, "dh_t_out")
+    X(DH_T_ACQ, "dh_t_acq") X(DH_T_JOB, "dh_t_job") X(DH_T_SCAN, "dh_t_scan") X(DH_T_OUT, "dh_t_out") \
+    X(DH_T_LDWAIT, "dh_t_ldwait") X(DH_T_FOLD, "dh_t_fold")
 
 #define MRZ_ST_ENUM(id, name) MRZ_ST_##id,
 enum { MRZ_SEQ_STATS_LIST(MRZ_ST_ENUM) MRZ_ST_N };
