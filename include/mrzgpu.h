@@ -341,6 +341,74 @@ int mrz_blake2b_final(mrz_blake2b *st, void *out_host, size_t outlen); /* frees 
 int mrz_blake2b_batch(mrz_ctx *ctx, const void *const *msgs, const int64_t *lens, int count, int where, size_t outlen,
                       uint8_t *out_host);
 
+/* ---- ar-mrzip index: TLSH digests, greedy order, ARZIP archives ---------- */
+
+/* The TLSH digest of every message, as compute_checksums takes it (ar-mrzip/ar-mrzip.cpp:137-172; vendor/tlsh built
+ * with 256 buckets and 3 checksum bytes): out_host + i * 139 receives the 138 upper-case hex characters and a NUL,
+ * or 139 NULs where the reference gives no digest (fewer than 50 bytes, an upper quartile of zero, at most half of the
+ * buckets hit); valid[i] (valid may be NULL) says which.  The archiver's own rule -- members of 500 bytes or less get
+ * no digest -- is NOT applied here.  A length above 4224281216 (the last length threshold; the reference's length
+ * code is undefined there and its 32-bit length wraps at 4 GiB) gives MRZ_E_UNSUPPORTED before any byte is read.
+ * opts may be NULL.  segment_len: bytes per workgroup, 0 = chosen by the batch's size, otherwise
+ * MRZ_TLSH_SEGMENT_MIN .. MRZ_TLSH_SEGMENT_MAX (else MRZ_E_ARG); the digests do not depend on it. */
+#define MRZ_TLSH_SEGMENT_MIN 64
+#define MRZ_TLSH_SEGMENT_MAX (1ll << 30)
+typedef struct {
+    int64_t segment_len;
+    int64_t reserved[3]; /* 0 */
+} mrz_tlsh_opts;
+int mrz_tlsh_batch(mrz_ctx *ctx, const void *const *msgs, const int64_t *lens, int count, int where,
+                   const mrz_tlsh_opts *opts, char *out_host, uint8_t *valid);
+/* the length code (0..169) a digest carries for a message of `len` bytes; host only */
+int mrz_tlsh_length_code(int64_t len);
+
+/* The greedy similarity order of ar-mrzip.cpp:408-437 over n digests of 137 bytes each (host memory, the caller's
+ * order): perm_out[k] = index of the member that comes k-th.  One launch per step scores every remaining member
+ * against the current head; "no byte in common with anything" moves the head of the list, as in the reference. */
+int mrz_ar_order(mrz_ctx *ctx, const uint8_t *digests137, int64_t n, int32_t *perm_out);
+
+/* create() of ar-mrzip (ar-mrzip.cpp:395-532) over members in memory: BLAKE2b-512 and TLSH of every member, the order,
+ * the collapse of exact duplicates and the ARZIP framing.  `where` says where every members[i].data lives, out_where
+ * where `out` does; with device output the payload is placed by device copies.  out == NULL is the sizing call (only
+ * the checksums are taken): *out_len is set and nothing is written.  out_cap too small: MRZ_E_ARG with *out_len set.
+ * A member above 4224281216 bytes: MRZ_E_UNSUPPORTED before any byte is read.  mtime is opaque.  info may be NULL. */
+typedef struct {
+    const char *name;
+    uint32_t name_len;
+    uint32_t reserved;
+    uint64_t mtime;
+    const void *data;
+    int64_t size;
+} mrz_ar_member;
+typedef struct {
+    int64_t unique_bytes;    /* payload bytes */
+    int64_t duplicate_bytes; /* bytes of members that share an earlier member's payload */
+    int64_t members_hashed;  /* members whose TLSH digest was taken (more than 500 bytes) */
+    int64_t metadata_size;
+} mrz_ar_info;
+int mrz_ar_create(mrz_ctx *ctx, const mrz_ar_member *members, int64_t n, int where, void *out, int out_where,
+                  int64_t out_cap, int64_t *out_len, mrz_ar_info *info);
+
+/* Host only: the records of an ARZIP archive in host memory.  MRZ_E_CORRUPT unless the magic is there, the records
+ * consume metadata_size exactly and every offset + size lies inside the payload.  entries == NULL counts only;
+ * otherwise up to `cap` entries are written (MRZ_E_ARG if there are more).  Offsets other than `offset` count from
+ * the start of the archive; `offset` counts from *payload_at. */
+typedef struct {
+    uint64_t mtime;
+    int64_t size;
+    int64_t offset;
+    int64_t record_at; /* the record: 24 bytes of numbers, 64 of BLAKE2b-512 at +24, 137 of TLSH at +88 */
+    int64_t name_at;
+    uint32_t name_len;
+    uint32_t reserved;
+} mrz_ar_entry;
+int mrz_ar_parse(const void *ar, int64_t n, mrz_ar_entry *entries, int64_t cap, int64_t *count, int64_t *payload_at);
+
+/* Checks every distinct member of an archive (host or device memory) against its stored BLAKE2b-512 with
+ * mrz_blake2b_batch.  *n_bad: records whose bytes do not match; *first_bad: the first of them in archive order, -1
+ * when there is none.  A malformed archive is MRZ_E_CORRUPT as in mrz_ar_parse. */
+int mrz_ar_verify(mrz_ctx *ctx, const void *ar, int64_t n, int where, int64_t *first_bad, int64_t *n_bad);
+
 /* ---- rs-mrzip encoder (the "next" row after the rzip stage) ------------------ */
 
 /* Replaces encode() of rs-mrzip (rs-mrzip/rs-mrzip.c:119-158): for every 223-byte row

@@ -68,6 +68,32 @@ class ArchiveRangeInfo(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TlshOpts(ctypes.Structure):
+    """mrz_tlsh_opts (include/mrzgpu.h)."""
+    _fields_ = [("segment_len", ctypes.c_int64), ("reserved", ctypes.c_int64 * 3)]
+
+
+class ArMember(ctypes.Structure):
+    """mrz_ar_member (include/mrzgpu.h)."""
+    _fields_ = [("name", ctypes.c_char_p), ("name_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("mtime", ctypes.c_uint64), ("data", ctypes.c_void_p), ("size", ctypes.c_int64)]
+
+
+class ArInfo(ctypes.Structure):
+    """mrz_ar_info (include/mrzgpu.h)."""
+    _fields_ = [(n, ctypes.c_int64) for n in ("unique_bytes", "duplicate_bytes", "members_hashed", "metadata_size")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ArEntry(ctypes.Structure):
+    """mrz_ar_entry (include/mrzgpu.h)."""
+    _fields_ = [("mtime", ctypes.c_uint64), ("size", ctypes.c_int64), ("offset", ctypes.c_int64),
+                ("record_at", ctypes.c_int64), ("name_at", ctypes.c_int64), ("name_len", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 class Control(ctypes.Structure):
     """The rzip_control fields rzip_fd reads for `mrzip -n` (include/mrzgpu_host.h)."""
     _fields_ = [("rzip_compression_level", ctypes.c_int), ("compression_level", ctypes.c_int),
@@ -192,6 +218,15 @@ def load_library(path=None):
         lib.mrz_blake2b_update.argtypes = [vp, vp, ctypes.c_size_t, ci]
         lib.mrz_blake2b_final.argtypes = [vp, vp, ctypes.c_size_t]
         lib.mrz_blake2b_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci, ctypes.c_size_t, vp]
+    if hasattr(lib, "mrz_tlsh_batch"):
+        lib.mrz_tlsh_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ci, ci, ctypes.POINTER(TlshOpts), vp,
+                                       vp]
+        lib.mrz_tlsh_length_code.argtypes = [i64]
+        lib.mrz_ar_order.argtypes = [vp, vp, i64, vp]
+        lib.mrz_ar_create.argtypes = [vp, ctypes.POINTER(ArMember), i64, ci, vp, ci, i64, ctypes.POINTER(i64),
+                                      ctypes.POINTER(ArInfo)]
+        lib.mrz_ar_parse.argtypes = [vp, i64, ctypes.POINTER(ArEntry), i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        lib.mrz_ar_verify.argtypes = [vp, vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     if hasattr(lib, "mrz_rs_encode"):
         lib.mrz_rs_encoded_size.argtypes = [i64]
         lib.mrz_rs_encoded_size.restype = i64
@@ -775,6 +810,95 @@ class RzipContext:
         _check(self.lib, self.lib.mrz_blake2b_batch(self.ctx, ptrs, lens, len(prep), prep[0][2], outlen, out),
                self.ctx)
         return [out.raw[i * outlen:(i + 1) * outlen] for i in range(len(prep))]
+
+    # ---- ar-mrzip index (ar-mrzip/ar-mrzip.cpp:137-172, 395-532) ----
+    def _need_ar(self):
+        if not hasattr(self.lib, "mrz_tlsh_batch"):
+            raise MrzError("this libmrzgpu has no mrz_tlsh_batch / mrz_ar_*: rebuild it")
+
+    def tlsh_batch(self, msgs, segment_len=0):
+        """mrz_tlsh_batch: the 138-character TLSH digest of every message, "" where it has none.  msgs: all host or
+        all device memory ((pointer, length) pairs or tensors)."""
+        self._need_ar()
+        prep = [_as_ptr(m) for m in msgs]
+        if not prep:
+            return []
+        if len({p[2] for p in prep}) > 1:
+            raise MrzError("tlsh_batch: the messages are all host or all device memory")
+        n = len(prep)
+        ptrs = (ctypes.c_void_p * n)(*[p[0] for p in prep])
+        lens = (ctypes.c_int64 * n)(*[p[1] for p in prep])
+        out = ctypes.create_string_buffer(139 * n)
+        valid = (ctypes.c_uint8 * n)()
+        opts = TlshOpts(segment_len)
+        _check(self.lib, self.lib.mrz_tlsh_batch(self.ctx, ptrs, lens, n, prep[0][2], ctypes.byref(opts), out, valid),
+               self.ctx)
+        res = [out.raw[139 * i:139 * i + 138].rstrip(b"\0").decode() for i in range(n)]
+        assert all(bool(r) == bool(v) and len(r) in (0, 138) for r, v in zip(res, valid))
+        return res
+
+    def ar_order(self, digests):
+        """mrz_ar_order: the greedy order of 137-byte digests, as a list of indices"""
+        self._need_ar()
+        n = len(digests)
+        if any(len(d) != 137 for d in digests):
+            raise MrzError("ar_order: a digest has 137 bytes")
+        blob = b"".join(bytes(d) for d in digests)
+        perm = (ctypes.c_int32 * max(n, 1))()
+        _check(self.lib, self.lib.mrz_ar_order(self.ctx, blob, n, perm), self.ctx)
+        return list(perm[:n])
+
+    def ar_create(self, members, out=None):
+        """mrz_ar_create over (name bytes, mtime, data) members, data all host or all device memory.  Returns
+        (archive bytes, info dict); with out (a writable buffer in host or device memory) the archive goes there and
+        its length is returned in place of the bytes."""
+        self._need_ar()
+        prep = [_as_ptr(d) for _, _, d in members]
+        if len({p[2] for p in prep}) > 1:
+            raise MrzError("ar_create: the members are all host or all device memory")
+        where = prep[0][2] if prep else MEM_HOST
+        n = len(prep)
+        arr = (ArMember * max(n, 1))()
+        for a, (name, mtime, _), p in zip(arr, members, prep):
+            a.name, a.name_len, a.mtime, a.data, a.size = bytes(name), len(name), mtime, p[0], p[1]
+        need, info = ctypes.c_int64(), ArInfo()
+        _check(self.lib, self.lib.mrz_ar_create(self.ctx, arr, n, where, None, MEM_HOST, 0, ctypes.byref(need),
+                                                ctypes.byref(info)), self.ctx)
+        if out is None:
+            buf = ctypes.create_string_buffer(max(1, need.value))
+            optr, ocap, owhere = ctypes.cast(buf, ctypes.c_void_p), need.value, MEM_HOST
+        else:
+            optr, ocap, owhere, keep = _as_ptr(out)
+        got = ctypes.c_int64()
+        _check(self.lib, self.lib.mrz_ar_create(self.ctx, arr, n, where, optr, owhere, ocap, ctypes.byref(got),
+                                                ctypes.byref(info)), self.ctx)
+        assert got.value == need.value
+        return (buf.raw[:got.value] if out is None else got.value), info.as_dict()
+
+    def ar_verify(self, archive):
+        """mrz_ar_verify: (records whose bytes do not match their checksum, index of the first one or -1)"""
+        self._need_ar()
+        ptr, n, where, keep = _as_ptr(archive)
+        first, bad = ctypes.c_int64(), ctypes.c_int64()
+        _check(self.lib, self.lib.mrz_ar_verify(self.ctx, ptr, n, where, ctypes.byref(first), ctypes.byref(bad)),
+               self.ctx)
+        return bad.value, first.value
+
+
+def ar_parse(archive, lib=None):
+    """mrz_ar_parse (host only): the records of an ARZIP archive in archive order, as dicts with name, mtime, size,
+    offset, checksum, digest and data; a malformed archive raises MrzError with .rc == MRZ_E_CORRUPT."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_ar_parse"):
+        raise MrzError("this libmrzgpu has no mrz_ar_parse: rebuild it")
+    ar = bytes(archive)
+    count, pay = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib, lib.mrz_ar_parse(ar, len(ar), None, 0, ctypes.byref(count), ctypes.byref(pay)))
+    ents = (ArEntry * max(1, count.value))()
+    _check(lib, lib.mrz_ar_parse(ar, len(ar), ents, count.value, ctypes.byref(count), ctypes.byref(pay)))
+    return [{"name": ar[e.name_at:e.name_at + e.name_len], "mtime": e.mtime, "size": e.size, "offset": e.offset,
+             "checksum": ar[e.record_at + 24:e.record_at + 88], "digest": ar[e.record_at + 88:e.record_at + 225],
+             "data": ar[pay.value + e.offset:pay.value + e.offset + e.size]} for e in ents[:count.value]]
 
 
 def rzip_buffer(data, level=7, window=0, unlimited=False, ramsize=60 << 30, device=0, lib=None):

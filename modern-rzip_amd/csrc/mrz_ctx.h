@@ -171,5 +171,9 @@ static inline int mrz_grow_keep(mrz_ctx *ctx, T **ptr, int64_t *cap, int64_t wan
 // (re)allocates the front end's buffers for passes of up to `tiles` tiles and lists of up to `entries` candidates
 int mrz_fe_reserve(mrz_ctx *ctx, int64_t tiles, int64_t entries);
 
+// mrz_tlsh_batch over messages that are in device memory (d_msgs: a host array of their device addresses)
+int mrz_tlsh_device_batch(mrz_ctx *ctx, const uint8_t *const *d_msgs, const int64_t *lens, int count,
+                          const mrz_tlsh_opts *opts, char *out_host, uint8_t *valid);
+
 // resolves a caller buffer to a device pointer (staging host memory on the ctx stream)
 int mrz_stage_input(mrz_ctx *ctx, const void *buf, int64_t n, int where, const uint8_t **dev);
