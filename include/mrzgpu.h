@@ -201,6 +201,16 @@ int mrz_schedule_info(const mrz_ctx *ctx, int64_t out[4]);
  * buffers with); returns when the source may be reused */
 int mrz_copy_to_device(mrz_ctx *ctx, void *dst_device, const void *src_host, int64_t n);
 int mrz_copy_device(mrz_ctx *ctx, void *dst_device, const void *src_device, int64_t n);
+/* n device -> device copies in ONE launch on the ctx stream: lens[i] bytes from src[i] to dst[i].  src, dst and lens are
+ * HOST arrays (of device pointers and lengths); they are turned into one table, uploaded once, and one kernel
+ * (mrz_seg_copy_kernel) moves every segment.  Ordered on the ctx stream like mrz_copy_device,
+ * and like it the call returns when the arrays may be reused.  n == 0 and lens[i] == 0 are fine (such a segment's
+ * pointers are not looked at); a negative length, or a null pointer with a positive length, is MRZ_E_ARG before
+ * anything is copied.  Sources may overlap each other (two members may share a payload).  THE CALLER'S CONTRACT: no
+ * destination overlaps another destination or any source -- the segments are copied concurrently, in no order.
+ * Nothing outside [dst[i], dst[i] + lens[i]) is written.  Fast path: src[i] and dst[i] congruent modulo 16 (16 bytes
+ * per lane); congruent modulo 4 only: 4 bytes per lane; otherwise byte by byte. */
+int mrz_copy_device_batch(mrz_ctx *ctx, const void *const *src, void *const *dst, const int64_t *lens, int64_t n);
 /* The window's BYTES when its ranges live on several GPUs (one process per GPU).  The reference maps the whole file and
  * single_match_len compares anywhere in it (src/rzip.c:372-397; -U: one chunk = the file, :881-882).  Here every rank
  * keeps its range in its own HBM as a shareable physical allocation (HIP virtual memory management):
@@ -409,6 +419,32 @@ int mrz_ar_parse(const void *ar, int64_t n, mrz_ar_entry *entries, int64_t cap, 
  * when there is none.  A malformed archive is MRZ_E_CORRUPT as in mrz_ar_parse. */
 int mrz_ar_verify(mrz_ctx *ctx, const void *ar, int64_t n, int where, int64_t *first_bad, int64_t *n_bad);
 
+/* extract() of ar-mrzip (ar-mrzip.cpp:540-779) over an archive in memory, without the files: the bytes of the selected
+ * members, packed in selection order.  `ar` is host or device memory per `where`, `out` per out_where.
+ *   which / n_which   indices into the archive's records, in archive order as mrz_ar_parse numbers them; which == NULL
+ *                     means every member (n_which is ignored).  An index out of range is MRZ_E_ARG.  A member may be
+ *                     selected more than once, and members that share a payload each get their own copy, as the
+ *                     reference writes every file.
+ *   out_offsets       HOST memory, n_which + 1 entries (members + 1 with which == NULL): entry k of the selection is
+ *                     written at out + out_offsets[k]; the last entry is the total.
+ *   out == NULL       the sizing call: only out_offsets and info->members / distinct_payloads / bytes_out are filled.
+ *   out_cap           smaller than the total: MRZ_E_ARG, with the offsets filled and nothing written.
+ *   flags             MRZ_AR_VERIFY: every distinct selected (offset, size) is hashed once (mrz_blake2b_batch) and held
+ *                     against the stored BLAKE2b-512 of every selected record: info->n_bad counts the selection entries
+ *                     whose bytes do not match, info->first_bad is the first such entry (-1: none).  The bytes are
+ *                     delivered all the same and the call returns MRZ_OK -- as mrz_ar_verify reports.
+ * A malformed archive is MRZ_E_CORRUPT under the rules of mrz_ar_parse.  Device to device the payloads move with one
+ * mrz_copy_device_batch; host to host is memcpy, and the device only takes the hashes.  info may be NULL. */
+#define MRZ_AR_VERIFY 1
+typedef struct {
+    int64_t members;           /* entries of the selection */
+    int64_t distinct_payloads; /* distinct (offset, size) among them */
+    int64_t bytes_out;         /* out_offsets[members] */
+    int64_t n_bad, first_bad;  /* MRZ_AR_VERIFY; 0 and -1 without it */
+} mrz_ar_extract_info;
+int mrz_ar_extract(mrz_ctx *ctx, const void *ar, int64_t n, int where, const int64_t *which, int64_t n_which, void *out,
+                   int out_where, int64_t out_cap, int64_t *out_offsets, int flags, mrz_ar_extract_info *info);
+
 /* ---- rs-mrzip encoder (the "next" row after the rzip stage) ------------------ */
 
 /* Replaces encode() of rs-mrzip (rs-mrzip/rs-mrzip.c:119-158): for every 223-byte row
@@ -536,6 +572,26 @@ int mrz_runzip_range(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s
                      int chunk_bytes, int64_t first, int64_t count, void *out, int out_where, mrz_range_info *info);
 int mrz_runzip_origins(mrz_ctx *ctx, const void *s0, int64_t s0_len, int64_t s1_len, int where, int chunk_bytes,
                        int64_t first, int64_t count, int64_t *origins, int out_where, mrz_range_info *info);
+
+/* Many ranges of one chunk in one call: ONE parse of stream 0, one table upload (16 bytes per range) and one launch
+ * (mrz_uz_resolve_multi_kernel), whatever n_ranges is.  `ranges` is HOST memory, in any order; ranges may overlap or
+ * be identical, and count == 0 is allowed.  The output is packed: range k begins at element sum(count_j, j < k);
+ * exactly sum(count) bytes (mrz_runzip_ranges) or int64 (mrz_runzip_origins_multi) are written, nothing outside them.
+ * The result is the concatenation of what mrz_runzip_range / mrz_runzip_origins give for each range in turn;
+ * info->total_hops is the sum of those calls' values and info->max_hops their maximum.  Whole-stream validation,
+ * MRZ_E_CORRUPT cases, `where` / out_where, the alignment rule for device origins and the absence of a CRC check are
+ * those calls'.  Any one bad range (first < 0, count < 0, first + count > chunk_len) is MRZ_E_ARG after the parse, with
+ * info->chunk_len set and nothing written.  sum(count) == 0 is MRZ_OK and takes out == NULL; n_ranges == 0 takes
+ * ranges == NULL. */
+typedef struct {
+    int64_t first, count;
+} mrz_byte_range;
+int mrz_runzip_ranges(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
+                      int chunk_bytes, const mrz_byte_range *ranges, int64_t n_ranges, void *out, int out_where,
+                      mrz_range_info *info);
+int mrz_runzip_origins_multi(mrz_ctx *ctx, const void *s0, int64_t s0_len, int64_t s1_len, int where, int chunk_bytes,
+                             const mrz_byte_range *ranges, int64_t n_ranges, int64_t *origins, int out_where,
+                             mrz_range_info *info);
 
 #ifdef __cplusplus
 }

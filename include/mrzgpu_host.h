@@ -159,6 +159,42 @@ typedef struct {
 int mrz_runzip_buffer_range_ex(int device, const void *mrz, int64_t n, int64_t first, int64_t count, void *out,
                                int out_where, int64_t *file_len, mrz_archive_range_info *info);
 
+/* Many ranges of the file in one call, over -n and -l archives alike.  `ranges` (host memory) in any order, overlapping
+ * or identical ranges and count == 0 allowed; the output is packed in list order and is, byte for byte, the
+ * concatenation of mrz_runzip_buffer_range_ex over the ranges.  Header rules, *file_len, MRZ_E_UNSUPPORTED,
+ * MRZ_E_CORRUPT and MRZ_E_ARG follow that function: against a header that carries the size one bad range (first < 0,
+ * count < 0, an end beyond the file) is MRZ_E_ARG before any device work; without a size the chunks are walked for the
+ * length first.  sum(count) == 0 takes out == NULL.  Behind a header that carries the size the walk stops behind the
+ * last chunk any range touches; a chunk no range touches does no device work.
+ * Per touched chunk: every range is clipped to the chunk, ALL clipped parts are resolved by one
+ * mrz_runzip_origins_multi -- stream 0 is parsed once per chunk, whatever the number of ranges --, the span and gather
+ * kernels and the prefix decode of mrz_runzip_buffer_range_ex run once over the flat origins, and one
+ * mrz_copy_device_batch moves the chunk's bytes to their places (parts that follow each other in the output are
+ * gathered in place instead).
+ * info: chunks_in_range counts each touched chunk once, s1_blocks_touched each block once per chunk; the hops are
+ * summed / maxed over all parts; the byte counts are what was moved.
+ * KNOWN COST, kept on purpose: per stream-1 block ONE interval [lowest, highest] is kept.  Two far-apart ranges in one
+ * CTYPE_NONE block upload the bytes between them (for an LZ4 block the prefix is needed anyway). */
+int mrz_runzip_buffer_ranges(int device, const void *mrz, int64_t n, const mrz_byte_range *ranges, int64_t n_ranges,
+                             void *out, int out_where, int64_t *file_len, mrz_archive_range_info *info);
+
+/* mrz_ar_extract (mrzgpu.h: selection, offsets, sizing call, out_cap, MRZ_AR_VERIFY, info) over an ARZIP archive that is
+ * what a -n / -l .mrz (host memory) decodes to; nothing of it is decoded that is not asked for:
+ *   1. bytes [0, 13) give the magic and metadata_size -- a wrong magic, a .mrz that decodes to fewer than 13 bytes or
+ *      metadata beyond the decoded length are MRZ_E_CORRUPT;
+ *   2. bytes [13, 13 + metadata_size) come to the host and are parsed (MRZ_E_CORRUPT as in mrz_ar_parse: every
+ *      offset + size is held against the decoded length);
+ *   3. the distinct selected payloads, ascending by offset, are decoded by ONE mrz_runzip_buffer_ranges call into
+ *      device memory, and one mrz_copy_device_batch places duplicates and the selection's order (host output: one copy
+ *      to the host, then memcpy);
+ *   4. with MRZ_AR_VERIFY the hashes are taken over those device bytes.
+ * The three range calls share one context but not the parse: stream 0 of a chunk that holds the head, the metadata and a
+ * payload is parsed three times.  range_info (may be NULL) sums the three calls (max_hops: their maximum).  Archive
+ * refusals (MRZ_E_UNSUPPORTED, MRZ_E_CORRUPT) are mrz_runzip_buffer_ranges'. */
+int mrz_ar_extract_mrz(int device, const void *mrz, int64_t n, const int64_t *which, int64_t n_which, void *out,
+                       int out_where, int64_t out_cap, int64_t *out_offsets, int flags, mrz_ar_extract_info *info,
+                       mrz_archive_range_info *range_info);
+
 #ifdef __cplusplus
 }
 #endif

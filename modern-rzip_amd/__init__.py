@@ -33,13 +33,15 @@ from .binding import (  # noqa: E402,F401
     runzip_buffer,
     runzip_buffer_range,
     runzip_buffer_range_ex,
+    runzip_buffer_ranges,
     rzip_pipeline,
     ar_parse,
+    ar_extract_mrz,
     MEM_HOST,
     MEM_DEVICE,
 )
 
 __all__ = [
     "MrzError", "RzipContext", "WindowPart", "WindowMap", "window_granularity", "ChunkResult", "Stats", "Timings", "Control", "lib_path", "load_library",
-    "chunk_bytes", "rzip_buffer", "rzip_buffer_lz4", "rzip_stream_buffer", "rzip_fd", "runzip_buffer", "runzip_buffer_range", "runzip_buffer_range_ex", "rzip_pipeline", "ar_parse", "MEM_HOST", "MEM_DEVICE",
+    "chunk_bytes", "rzip_buffer", "rzip_buffer_lz4", "rzip_stream_buffer", "rzip_fd", "runzip_buffer", "runzip_buffer_range", "runzip_buffer_range_ex", "runzip_buffer_ranges", "rzip_pipeline", "ar_parse", "ar_extract_mrz", "MEM_HOST", "MEM_DEVICE",
 ]

@@ -59,6 +59,31 @@ class RangeInfo(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ByteRange(ctypes.Structure):
+    """mrz_byte_range (include/mrzgpu.h)."""
+    _fields_ = [("first", ctypes.c_int64), ("count", ctypes.c_int64)]
+
+
+class ArExtractInfo(ctypes.Structure):
+    """mrz_ar_extract_info (include/mrzgpu.h)."""
+    _fields_ = [(n, ctypes.c_int64) for n in ("members", "distinct_payloads", "bytes_out", "n_bad", "first_bad")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _byte_ranges(ranges):
+    ranges = list(ranges)
+    return (ByteRange * max(len(ranges), 1))(*[ByteRange(int(a), int(c)) for a, c in ranges]), len(ranges)
+
+
+def _packed_len(ranges):
+    """bytes the packed output of a range list holds; 0 for a list the library refuses without writing"""
+    if any(a < 0 or c < 0 or a + c >= 1 << 63 for a, c in ranges):
+        return 0
+    return sum(c for _, c in ranges)
+
+
 class ArchiveRangeInfo(ctypes.Structure):
     """mrz_archive_range_info (include/mrzgpu_host.h)."""
     _fields_ = [(n, ctypes.c_int64) for n in ("chunks_in_range", "total_hops", "max_hops", "s0_lz4_bytes",
@@ -169,6 +194,8 @@ def load_library(path=None):
         lib.mrz_set_xcd.argtypes = [vp, ci]
         lib.mrz_copy_to_device.argtypes = [vp, vp, vp, i64]
         lib.mrz_copy_device.argtypes = [vp, vp, vp, i64]
+    if hasattr(lib, "mrz_copy_device_batch"):
+        lib.mrz_copy_device_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i64]
     if hasattr(lib, "mrz_window_map_create"):
         lib.mrz_window_granularity.argtypes = [ci]
         lib.mrz_window_granularity.restype = i64
@@ -238,6 +265,20 @@ def load_library(path=None):
         rip = ctypes.POINTER(RangeInfo)
         lib.mrz_runzip_range.argtypes = [vp, vp, i64, vp, i64, ci, ci, i64, i64, vp, ci, rip]
         lib.mrz_runzip_origins.argtypes = [vp, vp, i64, i64, ci, ci, i64, i64, vp, ci, rip]
+    if hasattr(lib, "mrz_runzip_ranges"):
+        rip, brp = ctypes.POINTER(RangeInfo), ctypes.POINTER(ByteRange)
+        lib.mrz_runzip_ranges.argtypes = [vp, vp, i64, vp, i64, ci, ci, brp, i64, vp, ci, rip]
+        lib.mrz_runzip_origins_multi.argtypes = [vp, vp, i64, i64, ci, ci, brp, i64, vp, ci, rip]
+    if hasattr(lib, "mrz_runzip_buffer_ranges"):
+        lib.mrz_runzip_buffer_ranges.argtypes = [ci, vp, i64, ctypes.POINTER(ByteRange), i64, vp, ci, ctypes.POINTER(i64),
+                                                 ctypes.POINTER(ArchiveRangeInfo)]
+    if hasattr(lib, "mrz_ar_extract"):
+        i64p = ctypes.POINTER(i64)
+        lib.mrz_ar_extract.argtypes = [vp, vp, i64, ci, i64p, i64, vp, ci, i64, i64p, ci, ctypes.POINTER(ArExtractInfo)]
+    if hasattr(lib, "mrz_ar_extract_mrz"):
+        i64p = ctypes.POINTER(i64)
+        lib.mrz_ar_extract_mrz.argtypes = [ci, vp, i64, i64p, i64, vp, ci, i64, i64p, ci, ctypes.POINTER(ArExtractInfo),
+                                           ctypes.POINTER(ArchiveRangeInfo)]
     if hasattr(lib, "mrz_runzip_buffer"):
         lib.mrz_runzip_buffer.argtypes = [ci, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
     if hasattr(lib, "mrz_runzip_buffer_range"):
@@ -409,6 +450,18 @@ class RzipContext:
         ptr, n, where, keep = _as_ptr(src)
         fn = self.lib.mrz_copy_device if where == MEM_DEVICE else self.lib.mrz_copy_to_device
         _check(self.lib, fn(self.ctx, ctypes.c_void_p(dst_ptr), ptr, n), self.ctx)
+
+    def copy_device_batch(self, segments):
+        """mrz_copy_device_batch: every (src device address, dst device address, nbytes) of `segments` in one launch on
+        the ctx stream.  Destinations must not overlap each other or any source."""
+        if not hasattr(self.lib, "mrz_copy_device_batch"):
+            raise MrzError("this libmrzgpu has no mrz_copy_device_batch: rebuild it")
+        segs = list(segments)
+        n = len(segs)
+        src = (ctypes.c_void_p * max(n, 1))(*[s[0] for s in segs])
+        dst = (ctypes.c_void_p * max(n, 1))(*[s[1] for s in segs])
+        lens = (ctypes.c_int64 * max(n, 1))(*[int(s[2]) for s in segs])
+        _check(self.lib, self.lib.mrz_copy_device_batch(self.ctx, src, dst, lens, n), self.ctx)
 
     def window_scan(self, range_bytes, range_start, chunk_n, seg_start, max_span, min_mask, p_done=0, cap=1 << 20,
                     out=None):
@@ -781,6 +834,54 @@ class RzipContext:
         self._check_range(rc, info)
         return (arr[:count] if out is None else None), info.as_dict()
 
+    def runzip_ranges(self, s0, s1, chunk_bytes_, ranges, out=None):
+        """mrz_runzip_ranges: the bytes of every (first, count) of `ranges`, packed in list order, after one parse of
+        stream 0.  Returns (bytes or None, info dict) as runzip_range; total_hops is summed and max_hops maxed over the
+        ranges."""
+        if not hasattr(self.lib, "mrz_runzip_ranges"):
+            raise MrzError("this libmrzgpu has no mrz_runzip_ranges: rebuild it")
+        p0, n0, w0, k0 = _as_ptr(s0)
+        p1, n1, w1, k1 = _as_ptr(s1)
+        if w0 != w1:
+            raise MrzError("runzip_ranges: both streams must live in the same memory space")
+        ranges = list(ranges)
+        arr, n = _byte_ranges(ranges)
+        total = _packed_len(ranges)
+        info = RangeInfo(-1, 0, 0)
+        if out is None:
+            buf = ctypes.create_string_buffer(max(1, total))
+            po, wo = ctypes.cast(buf, ctypes.c_void_p), MEM_HOST
+        else:
+            po, no, wo, ko = _as_ptr(out)
+            if no < total:
+                raise MrzError("runzip_ranges: the output buffer is smaller than the ranges asked for")
+        rc = self.lib.mrz_runzip_ranges(self.ctx, p0, n0, p1, n1, w0, chunk_bytes_, arr, n, po, wo, ctypes.byref(info))
+        self._check_range(rc, info)
+        return (buf.raw[:total] if out is None else None), info.as_dict()
+
+    def runzip_origins_multi(self, s0, s1_len, chunk_bytes_, ranges, out=None):
+        """mrz_runzip_origins_multi: the stream-1 offsets of every byte of every range, packed in list order.  Returns
+        (int64 numpy array or None, info dict) as runzip_origins."""
+        import numpy as np
+        if not hasattr(self.lib, "mrz_runzip_origins_multi"):
+            raise MrzError("this libmrzgpu has no mrz_runzip_origins_multi: rebuild it")
+        p0, n0, w0, k0 = _as_ptr(s0)
+        ranges = list(ranges)
+        arr, n = _byte_ranges(ranges)
+        total = _packed_len(ranges)
+        info = RangeInfo(-1, 0, 0)
+        if out is None:
+            res = np.empty(max(1, total), dtype=np.int64)
+            po, wo = ctypes.c_void_p(res.ctypes.data), MEM_HOST
+        else:
+            po, no, wo, ko = _as_ptr(out)
+            if no < total * 8:
+                raise MrzError("runzip_origins_multi: the output buffer is smaller than the ranges asked for")
+        rc = self.lib.mrz_runzip_origins_multi(self.ctx, p0, n0, s1_len, w0, chunk_bytes_, arr, n, po, wo,
+                                               ctypes.byref(info))
+        self._check_range(rc, info)
+        return (res[:total] if out is None else None), info.as_dict()
+
     def _check_range(self, rc, info):
         try:
             _check(self.lib, rc, self.ctx)
@@ -883,6 +984,71 @@ class RzipContext:
         _check(self.lib, self.lib.mrz_ar_verify(self.ctx, ptr, n, where, ctypes.byref(first), ctypes.byref(bad)),
                self.ctx)
         return bad.value, first.value
+
+
+    def ar_extract(self, archive, which=None, out=None, verify=False):
+        """mrz_ar_extract: the selected members (indices into ar_parse's list; None: all of them) of an archive in host
+        or device memory, packed in selection order.  Returns (bytes, offsets list, info dict); with `out` (a writable
+        buffer in host or device memory) the bytes go there and None is returned in their place."""
+        if not hasattr(self.lib, "mrz_ar_extract"):
+            raise MrzError("this libmrzgpu has no mrz_ar_extract: rebuild it")
+        ptr, n, where, keep = _as_ptr(archive)
+        return _ar_extract(self.lib, self.ctx, lambda *a: self.lib.mrz_ar_extract(self.ctx, ptr, n, where, *a), None,
+                           self._ar_count(ptr, n, where, which), which, out, verify)
+
+    def _ar_count(self, ptr, n, where, which):
+        """entries of the selection: with which=None the records are counted by mrz_ar_parse first"""
+        if which is not None:
+            return len(which)
+        if where == MEM_HOST:
+            count = ctypes.c_int64()
+            _check(self.lib, self.lib.mrz_ar_parse(ptr, n, None, 0, ctypes.byref(count), None))
+            return count.value
+        raise MrzError("ar_extract: which=None takes the archive in host memory (the offsets need one entry per record); "
+                       "pass the indices for an archive in device memory")
+
+
+def _ar_extract(lib, ctx, call, range_info, n_sel, which, out, verify):
+    """the two calls behind ar_extract / ar_extract_mrz: sizing, then the bytes.  call(which, n_which, out, out_where,
+    out_cap, offsets, flags, info[, range_info])"""
+    idx = None if which is None else (ctypes.c_int64 * max(n_sel, 1))(*[int(w) for w in which])
+    offs = (ctypes.c_int64 * (n_sel + 1))()
+    info = ArExtractInfo()
+    extra = () if range_info is None else (ctypes.byref(range_info),)
+    _check(lib, call(idx, n_sel, None, MEM_HOST, 0, offs, 0, ctypes.byref(info), *extra), ctx)
+    total = info.bytes_out
+    if out is None:
+        buf = ctypes.create_string_buffer(max(1, total))
+        po, cap, wo = ctypes.cast(buf, ctypes.c_void_p), total, MEM_HOST
+    else:
+        po, cap, wo, keep = _as_ptr(out)
+    _check(lib, call(idx, n_sel, po, wo, cap, offs, 1 if verify else 0, ctypes.byref(info), *extra), ctx)
+    return (buf.raw[:total] if out is None else None), list(offs), info.as_dict()
+
+
+def ar_extract_mrz(mrz, which, out=None, verify=False, device=0, lib=None):
+    """mrz_ar_extract_mrz: the selected members (a list of indices into the archive's records) of the ARZIP archive a
+    -n / -l .mrz held in host memory decodes to, decoding nothing that is not asked for.  Returns (bytes or None, offsets,
+    info dict, range_info dict); which=None (every member) needs two passes here: the records are counted first."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_ar_extract_mrz"):
+        raise MrzError("this libmrzgpu has no mrz_ar_extract_mrz: rebuild it")
+    ptr, n, where, keep = _as_ptr(mrz)
+    if where != MEM_HOST:
+        raise MrzError("ar_extract_mrz takes the archive in host memory")
+    rinfo = ArchiveRangeInfo()
+    if which is None:   # the count: bytes [5, 13) say how long the metadata is, the records in it are counted on the host
+        head, _, _ = runzip_buffer_ranges(mrz, [(0, 13)], device=device, lib=lib)
+        meta, _, _ = runzip_buffer_ranges(mrz, [(0, 13 + int.from_bytes(head[5:13], "big"))], device=device, lib=lib)
+        n_sel, at = 0, 13
+        while at + 229 <= len(meta):
+            at += 229 + int.from_bytes(meta[at + 225:at + 229], "big")
+            n_sel += 1
+    else:
+        n_sel = len(which)
+    data, offs, info = _ar_extract(lib, None, lambda *a: lib.mrz_ar_extract_mrz(device, ptr, n, *a), rinfo, n_sel, which,
+                                   out, verify)
+    return data, offs, info, rinfo.as_dict()
 
 
 def ar_parse(archive, lib=None):
@@ -1037,6 +1203,37 @@ def runzip_buffer_range_ex(mrz, first, count, out=None, device=0, lib=None):
         e.file_len = file_len.value if file_len.value >= 0 else None
         raise
     return (buf.raw[:max(0, count)] if out is None else None), file_len.value, info.as_dict()
+
+
+def runzip_buffer_ranges(mrz, ranges, out=None, device=0, lib=None):
+    """mrz_runzip_buffer_ranges: every (first, count) of `ranges` out of a -n / -l archive held in memory, packed in list
+    order; stream 0 of a chunk is parsed once whatever the number of ranges.  Returns (bytes or None, file_len, info dict)
+    as runzip_buffer_range_ex, and raises like it."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mrz_runzip_buffer_ranges"):
+        raise MrzError("this libmrzgpu has no mrz_runzip_buffer_ranges: rebuild it")
+    ptr, n, where, keep = _as_ptr(mrz)
+    if where != MEM_HOST:
+        raise MrzError("runzip_buffer_ranges takes the archive in host memory")
+    ranges = list(ranges)
+    arr, k = _byte_ranges(ranges)
+    total = _packed_len(ranges)
+    if out is None:
+        buf = ctypes.create_string_buffer(max(1, total))
+        po, wo = ctypes.cast(buf, ctypes.c_void_p), MEM_HOST
+    else:
+        po, no, wo, ko = _as_ptr(out)
+        if no < total:
+            raise MrzError("runzip_buffer_ranges: the output buffer is smaller than the ranges asked for")
+    file_len = ctypes.c_int64(-1)
+    info = ArchiveRangeInfo()
+    try:
+        _check(lib, lib.mrz_runzip_buffer_ranges(device, ptr, n, arr, k, po, wo, ctypes.byref(file_len),
+                                                 ctypes.byref(info)))
+    except MrzError as e:
+        e.file_len = file_len.value if file_len.value >= 0 else None
+        raise
+    return (buf.raw[:total] if out is None else None), file_len.value, info.as_dict()
 
 
 def rzip_pipeline(data, on_block, level=7, window=0, unlimited=False, ramsize=60 << 30, device=0, lib=None,

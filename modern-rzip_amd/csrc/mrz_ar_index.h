@@ -140,3 +140,14 @@ static inline int mrz_ar_read(const uint8_t *ar, int64_t have, int64_t n, std::v
     *payload_at = end;
     return MRZ_OK;
 }
+
+// The same verdicts from the head alone: head[0, head_len) is the start of an archive of total_len bytes that the
+// caller does not hold (mrz_ar_extract_mrz decodes nothing of it but these bytes).  head_len must be exactly
+// MRZ_AR_HEAD + metadata_size, or at least MRZ_AR_HEAD + metadata_size when the caller holds more (a whole archive):
+// fewer bytes are MRZ_E_CORRUPT like a truncated archive, and so is a total_len that cannot hold head_len.  No byte at
+// or behind head_len is read; the payload's extent, against which every offset + size is judged, comes from total_len.
+static inline int mrz_ar_read_prefix(const uint8_t *head, int64_t head_len, int64_t total_len,
+                                     std::vector<mrz_ar_rec> &recs, int64_t *payload_at) {
+    if (!head || head_len < 0 || total_len < head_len) return MRZ_E_CORRUPT;
+    return mrz_ar_read(head, head_len, total_len, recs, payload_at);
+}

@@ -186,6 +186,82 @@ struct mrz_arc_range {
     }
 };
 
+// A list of ranges of the file against the chunks (mrz_runzip_buffer_ranges): mrz_arc_range for many ranges at once.
+// The output is packed in list order: range k goes to output offset sum(count_j, j < k).  The caller walks the chunks,
+// asks for the parts of each one and adds its decoded length to `total`.
+struct mrz_arc_part {
+    int64_t lo, cnt;  // bytes [lo, lo + cnt) of the chunk ...
+    int64_t out_at;   // ... go to output offset out_at
+};
+
+struct mrz_arc_ranges {
+    const mrz_byte_range *ranges;
+    int64_t n;
+    std::vector<int64_t> out_base;  // where each range begins in the output (meaningless when bad)
+    bool size_known;
+    bool bad;          // no file has such a list: the walk goes on (without a size the length is owed), the work does not
+    int64_t sum;       // bytes asked for
+    int64_t last_end;  // the end of the last byte any non-empty range asks for: nothing behind it is needed
+    int64_t total;     // decoded bytes of the chunks passed so far
+
+    // against a header that carries the size: *file_len first, then the verdict on the list
+    int begin(const mrz_arc_header &h, const mrz_byte_range *ranges_, int64_t n_, int64_t *file_len) {
+        ranges = ranges_;
+        n = n_;
+        size_known = h.size_known();
+        bad = false;
+        sum = last_end = total = 0;
+        out_base.assign((size_t)n, 0);
+        if (size_known && file_len) *file_len = h.expected;
+        bool beyond = false;
+        for (int64_t k = 0; k < n && !bad; k++) {
+            const int64_t first = ranges[k].first, count = ranges[k].count;
+            if (first < 0 || count < 0 || count > INT64_MAX - first || count > INT64_MAX - sum) {
+                bad = true;
+                break;
+            }
+            out_base[(size_t)k] = sum;
+            sum += count;
+            if (count > 0 && first + count > last_end) last_end = first + count;
+            if (size_known && (first > h.expected || count > h.expected - first)) beyond = true;
+        }
+        return size_known && (bad || beyond) ? MRZ_E_ARG : MRZ_OK;
+    }
+    // the parts of the next chunk (chunk_len bytes from `total` on) that the ranges ask for, in list order; false: none
+    bool clip(int64_t chunk_len, std::vector<mrz_arc_part> &parts) const {
+        parts.clear();
+        if (bad || sum <= 0 || total >= last_end) return false;
+        for (int64_t k = 0; k < n; k++) {
+            const int64_t first = ranges[k].first, count = ranges[k].count;
+            if (count <= 0 || total >= first + count || total + chunk_len <= first) continue;
+            const int64_t a = first > total ? first : total;
+            const int64_t b = first + count < total + chunk_len ? first + count : total + chunk_len;
+            if (b <= a) continue;  // an empty chunk inside the range
+            parts.push_back(mrz_arc_part{ a - total, b - a, out_base[(size_t)k] + (a - first) });
+        }
+        return !parts.empty();
+    }
+    // the parts follow each other in the output without a gap: they can be written in place
+    static bool contiguous(const std::vector<mrz_arc_part> &parts) {
+        for (size_t k = 1; k < parts.size(); k++)
+            if (parts[k].out_at != parts[k - 1].out_at + parts[k - 1].cnt) return false;
+        return true;
+    }
+    bool covered() const { return size_known && total >= last_end; }  // nothing past the last range is looked at
+
+    // after the walk: the length where the header had none, and what is left to say about the list
+    int finish(int64_t *file_len) const {
+        if (!size_known) {
+            if (file_len) *file_len = total;
+            if (bad) return MRZ_E_ARG;
+            for (int64_t k = 0; k < n; k++)
+                if (ranges[k].first > total || ranges[k].count > total - ranges[k].first) return MRZ_E_ARG;
+        } else if (total < last_end)
+            return MRZ_E_CORRUPT;  // fewer bytes than the header promised
+        return MRZ_OK;
+    }
+};
+
 // A stream's blocks with the stream offset each one starts at (CTYPE_NONE: the bytes stay in the archive).
 struct mrz_arc_table {
     std::vector<mrz_arc_block> blocks;

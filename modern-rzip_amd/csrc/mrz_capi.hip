@@ -117,6 +117,7 @@ extern "C" void mrz_close(mrz_ctx *ctx) {
     if (ctx->rz_scratch) hipFree(ctx->rz_scratch);
     if (ctx->d_rz_out) hipFree(ctx->d_rz_out);
     if (ctx->d_rz_done) hipFree(ctx->d_rz_done);
+    if (ctx->seg_tab) hipFree(ctx->seg_tab);
     if (ctx->d_rs_tables) hipFree(ctx->d_rs_tables);
     if (ctx->d_rs_out) hipFree(ctx->d_rs_out);
     if (ctx->d_rs_dec) hipFree(ctx->d_rs_dec);

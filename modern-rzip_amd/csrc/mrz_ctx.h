@@ -82,6 +82,8 @@ struct mrz_ctx {
     int64_t rz_out_cap;
     unsigned *d_rz_done;
     int64_t rz_done_cap;
+    uint8_t *seg_tab;  // the segment table of the mrz_copy_device_batch call in flight (mrz_segcopy.hip)
+    int64_t seg_tab_cap;
     int have_chunk;
 
     // LZ4 / BLAKE2b scratch (owned by their translation units, freed in mrz_close)

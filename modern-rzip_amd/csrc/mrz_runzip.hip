@@ -503,6 +503,109 @@ __global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_resolve_kernel(const mr
     }
 }
 
+// ---- many ranges of a chunk in one launch (mrz_runzip_ranges / mrz_runzip_origins_multi) --------------------------
+// The ranges come as a table of n + 1 entries of 16 bytes: first[r], and prefix[r] = the sum of the counts in front of
+// range r (entry n holds the total).  Flat index i of the packed output belongs to the last r with prefix[r] <= i --
+// empty ranges share their prefix with their successor and are never found.
+struct mrz_uz_rng {
+    int64_t first, prefix;
+};
+
+__device__ __forceinline__ int64_t mrz_uz_find_rng(const mrz_uz_rng *__restrict__ rng, int64_t i, int64_t hi) {
+    int64_t lo = 0;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (rng[mid].prefix <= i)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// mrz_uz_resolve_kernel over the packed output of nrng ranges.  A wave owns 64 consecutive flat indices; it searches
+// once, with wave-uniform operands, for the range of its first index and for the record of that range's byte there; a
+// lane whose index lies beyond that range searches the table for itself, and one whose byte lies outside that record
+// (in front of it too: the ranges come in any order) searches the records for itself.  The walk, its hop limit, the
+// hdr->error = 2 exit and the statistics are those of mrz_uz_resolve_kernel, restated here so that kernel's code stays
+// what it is.  No LDS, nothing shared between workgroups, no wait on memory.
+template <bool ORIGINS>
+__global__ __launch_bounds__(MRZ_UZ_THREADS) void mrz_uz_resolve_multi_kernel(const mrz_urec *__restrict__ rec, int64_t nrec,
+                                                                              const uint8_t *__restrict__ s1,
+                                                                              const mrz_uz_rng *__restrict__ rng,
+                                                                              int64_t nrng, int64_t count,
+                                                                              void *__restrict__ dst,
+                                                                              mrz_uz_hdr *__restrict__ hdr) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t stride = (int64_t)gridDim.x * MRZ_UZ_THREADS;
+    int64_t sum_hops = 0, top_hops = 0;
+    const int64_t base0 = mrz_uz_uniform64((int64_t)blockIdx.x * MRZ_UZ_THREADS + (threadIdx.x - lane));
+    if (base0 >= count) return;  // the whole wave
+    for (int64_t base = base0; base < count; base += stride) {
+        // once per wave: the range of the first index, and the record of its byte
+        const int64_t g = mrz_uz_find_rng(rng, base, nrng - 1);
+        int64_t g_first = rng[g].first, g_at = rng[g].prefix;
+        const int64_t g_end = rng[g + 1].prefix;
+        int64_t r = mrz_uz_find(rec, g_first + (base - g_at), nrec - 1);
+        int64_t o = rec[r].out_pos, o_end = rec[r + 1].out_pos;
+        const int64_t i = base + lane;
+        int64_t hops = 0, origin = 0;
+        if (i < count) {
+            if (i >= g_end) {  // not the wave's range
+                const int64_t g2 = mrz_uz_find_rng(rng, i, nrng - 1);
+                g_first = rng[g2].first;
+                g_at = rng[g2].prefix;
+            }
+            int64_t x = g_first + (i - g_at), hi = nrec - 1;
+            if (x < o || x >= o_end) {  // not the wave's record
+                r = mrz_uz_find(rec, x, hi);
+                o = rec[r].out_pos;
+                o_end = rec[r + 1].out_pos;
+            }
+            while (true) {
+                const unsigned long long src = rec[r].src;
+                if (!(src & MRZ_UZ_MATCH)) {
+                    origin = (int64_t)src + (x - o);
+                    break;
+                }
+                if (hops >= nrec) {
+                    hdr->error = 2;
+                    break;
+                }
+                const int64_t dist = (int64_t)(src & ~MRZ_UZ_MATCH), len = o_end - o;
+                const int64_t span = len < dist ? len : dist;
+                const int64_t k = x - o;
+                x = o - dist + (k < span ? k : k % span);
+                hops++;
+                hi = r;
+                r = mrz_uz_find(rec, x, hi);
+                o = rec[r].out_pos;
+                o_end = rec[r + 1].out_pos;
+            }
+            if (ORIGINS)
+                ((int64_t *)dst)[i] = origin;
+            else
+                ((uint8_t *)dst)[i] = s1[origin];
+        }
+        sum_hops += hops;
+        top_hops = hops > top_hops ? hops : top_hops;
+    }
+    for (int d = 32; d; d >>= 1) {
+        sum_hops += mrz_shfl_xor64(sum_hops, d);
+        const int64_t t = mrz_shfl_xor64(top_hops, d);
+        top_hops = t > top_hops ? t : top_hops;
+    }
+    if (lane == 0 && sum_hops) {
+        atomicAdd(&hdr->total_hops, (unsigned long long)sum_hops);
+        unsigned long long seen = __hip_atomic_load(&hdr->max_hops, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        while ((unsigned long long)top_hops > seen) {
+            const unsigned long long was = atomicCAS(&hdr->max_hops, seen, (unsigned long long)top_hops);
+            if (was == seen) break;
+            seen = was;
+        }
+    }
+}
+
 // ---- range decode over a stream 1 that stays in its blocks (mrz_runzip_buffer_range_ex) ---------------------------
 // The origins of a range stay on the device; `starts` is the table of the chunk's stream-1 blocks as ascending offsets
 // in stream 1, starts[0] == 0 (an empty block shares its start with its successor and is never found).
@@ -825,6 +928,122 @@ extern "C" int mrz_runzip_origins(mrz_ctx *ctx, const void *s0, int64_t s0_len, 
                                   int64_t first, int64_t count, int64_t *origins, int out_where, mrz_range_info *info) {
     try {
         return uz_range(ctx, true, s0, s0_len, nullptr, s1_len, where, chunk_bytes, first, count, origins, out_where, info);
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+}
+
+// bytes or origins of many ranges, packed in list order: see include/mrzgpu.h.  uz_range with a table in place of
+// (first, count): one parse, one table upload, one launch.
+static int uz_ranges(mrz_ctx *ctx, bool want_origins, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len,
+                     int where, int chunk_bytes, const mrz_byte_range *ranges, int64_t n_ranges, void *out, int out_where,
+                     mrz_range_info *info) {
+    if (!ctx || !s0 || s0_len < 7 || s1_len < 0 || chunk_bytes < 1 || chunk_bytes > 8) return MRZ_E_ARG;
+    if (n_ranges < 0 || (n_ranges > 0 && !ranges)) return MRZ_E_ARG;
+    if (!want_origins && s1_len > 0 && !s1) return MRZ_E_ARG;
+    if ((where != MRZ_MEM_HOST && where != MRZ_MEM_DEVICE) || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE))
+        return MRZ_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    uz_parsed ps;
+    int rc = uz_parse(ctx, s0, s0_len, where, chunk_bytes, (n_ranges + 1) * (int64_t)sizeof(mrz_uz_rng), nullptr, 0, &ps);
+    if (rc) return rc;
+    const mrz_uz_hdr &h = ps.h;
+    if (h.final_state != MRZ_UZ_END || h.error || h.lit_total > s1_len) return MRZ_E_CORRUPT;
+    if (info) {
+        info->chunk_len = h.out_total;
+        info->total_hops = info->max_hops = 0;
+    }
+    std::vector<mrz_uz_rng> tab((size_t)n_ranges + 1);
+    int64_t count = 0;
+    for (int64_t k = 0; k < n_ranges; k++) {
+        const mrz_byte_range &g = ranges[k];
+        if (g.first < 0 || g.count < 0 || g.first > h.out_total || g.count > h.out_total - g.first) return MRZ_E_ARG;
+        if (g.count > INT64_MAX / 8 - count) return MRZ_E_ARG;  // more than any buffer holds
+        tab[(size_t)k] = mrz_uz_rng{ g.first, count };
+        count += g.count;
+    }
+    tab[(size_t)n_ranges] = mrz_uz_rng{ 0, count };
+    if (!count) return MRZ_OK;
+    if (!out) return MRZ_E_ARG;
+
+    // as in uz_range: a host-resident stream 1 stays where it is
+    const bool origins = want_origins || where == MRZ_MEM_HOST;
+    const bool direct = out_where == MRZ_MEM_DEVICE && origins == want_origins;
+    if (direct && want_origins && ((uintptr_t)out & 7)) return MRZ_E_ARG;
+    const int64_t item = origins ? 8 : 1;
+    void *d_dst = out;
+    if (!direct) {
+        rc = mrz_grow(ctx, &ctx->d_rz_out, &ctx->rz_out_cap, count * item);
+        if (rc) return rc;
+        d_dst = ctx->d_rz_out;
+    }
+    const mrz_uz_rng *d_rng = (const mrz_uz_rng *)ps.d_extra;
+    HIPCHK(ctx, hipMemcpyAsync(ps.d_extra, tab.data(), tab.size() * sizeof(mrz_uz_rng), hipMemcpyHostToDevice, s));
+    int cus = 0;
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    int64_t grid = (int64_t)(cus > 0 ? cus : 64) * 8;
+    const int64_t blocks = (count + MRZ_UZ_THREADS - 1) / MRZ_UZ_THREADS;
+    if (grid > blocks) grid = blocks;
+    if (origins)
+        hipLaunchKernelGGL(mrz_uz_resolve_multi_kernel<true>, dim3((unsigned)grid), dim3(MRZ_UZ_THREADS), 0, s, ps.d_rec,
+                           h.nrec, (const uint8_t *)nullptr, d_rng, n_ranges, count, d_dst, ps.d_hdr);
+    else
+        hipLaunchKernelGGL(mrz_uz_resolve_multi_kernel<false>, dim3((unsigned)grid), dim3(MRZ_UZ_THREADS), 0, s, ps.d_rec,
+                           h.nrec, (const uint8_t *)s1, d_rng, n_ranges, count, d_dst, ps.d_hdr);
+    HIPCHK(ctx, hipGetLastError());
+    mrz_uz_hdr after;
+    HIPCHK(ctx, hipMemcpyAsync(&after, ps.d_hdr, sizeof(after), hipMemcpyDeviceToHost, s));
+    std::vector<int64_t> h_org;
+    if (!direct && origins && !want_origins) {  // bytes asked for, stream 1 on the host
+        h_org.resize((size_t)count);
+        HIPCHK(ctx, hipMemcpyAsync(h_org.data(), d_dst, (size_t)count * 8, hipMemcpyDeviceToHost, s));
+    } else if (!direct)
+        HIPCHK(ctx, hipMemcpyAsync(out, d_dst, (size_t)(count * item), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (after.error) return after.error == 2 ? MRZ_E_STATE : MRZ_E_CORRUPT;
+    if (info) {
+        info->total_hops = (int64_t)after.total_hops;
+        info->max_hops = (int64_t)after.max_hops;
+    }
+    if (!h_org.empty()) {
+        std::vector<uint8_t> staged;
+        uint8_t *dst = (uint8_t *)out;
+        if (out_where == MRZ_MEM_DEVICE) {
+            staged.resize((size_t)count);
+            dst = staged.data();
+        }
+        const uint8_t *lit = (const uint8_t *)s1;
+        for (int64_t i = 0; i < count;) {  // runs of consecutive origins
+            int64_t j = i + 1;
+            while (j < count && h_org[(size_t)j] == h_org[(size_t)j - 1] + 1) j++;
+            memcpy(dst + i, lit + h_org[(size_t)i], (size_t)(j - i));
+            i = j;
+        }
+        if (out_where == MRZ_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpyAsync(out, dst, (size_t)count, hipMemcpyHostToDevice, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+    }
+    return MRZ_OK;
+}
+
+extern "C" int mrz_runzip_ranges(mrz_ctx *ctx, const void *s0, int64_t s0_len, const void *s1, int64_t s1_len, int where,
+                                 int chunk_bytes, const mrz_byte_range *ranges, int64_t n_ranges, void *out, int out_where,
+                                 mrz_range_info *info) {
+    try {
+        return uz_ranges(ctx, false, s0, s0_len, s1, s1_len, where, chunk_bytes, ranges, n_ranges, out, out_where, info);
+    } catch (const std::bad_alloc &) {
+        return MRZ_E_NOMEM;
+    }
+}
+
+extern "C" int mrz_runzip_origins_multi(mrz_ctx *ctx, const void *s0, int64_t s0_len, int64_t s1_len, int where,
+                                        int chunk_bytes, const mrz_byte_range *ranges, int64_t n_ranges, int64_t *origins,
+                                        int out_where, mrz_range_info *info) {
+    try {
+        return uz_ranges(ctx, true, s0, s0_len, nullptr, s1_len, where, chunk_bytes, ranges, n_ranges, origins, out_where,
+                         info);
     } catch (const std::bad_alloc &) {
         return MRZ_E_NOMEM;
     }

@@ -228,9 +228,12 @@ struct S1Piece {
     int64_t at;    // where the piece begins in its block
 };
 
-// Bytes [lo, lo + cnt) of one chunk into d_out (device memory): origins, spans, the touched blocks' prefixes, gather.
-int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, int where0, const mrz_arc_table &s1,
-                       int64_t s1_len, int cb, int64_t lo, int64_t cnt, uint8_t *d_out, mrz_archive_range_info &acc) {
+// `cnt` bytes of one chunk into d_out (device memory): origins, spans, the touched blocks' prefixes, gather.  Which
+// bytes they are is the resolver's business: resolve(d_org, &ri) leaves their cnt origins, in the order of d_out, in
+// device memory at d_org -- one range (mrz_runzip_origins) or the packed parts of many (mrz_runzip_origins_multi).
+template <class Resolve>
+int chunk_blocks(mrz_ctx *ctx, int cus, const mrz_arc_table &s1, int64_t cnt, Resolve &&resolve, uint8_t *d_out,
+                 mrz_archive_range_info &acc) {
     std::vector<int64_t> starts;
     std::vector<S1Piece> pieces;
     for (size_t k = 0; k < s1.blocks.size(); k++) {
@@ -250,7 +253,7 @@ int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, in
     mrz_uz_span *d_span = (mrz_uz_span *)(tab.p + o_span);
 
     mrz_range_info ri;
-    int rc = mrz_runzip_origins(ctx, s0, s0_len, s1_len, where0, cb, lo, cnt, d_org, MRZ_MEM_DEVICE, &ri);
+    int rc = resolve(d_org, &ri);
     if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // the device's reading of the records differs from the length walk's
     if (rc) return rc;
     acc.chunks_in_range++;
@@ -325,6 +328,139 @@ int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, in
     }
     HIPCHK(ctx, mrz_launch_block_gather(s, cus, d_org, cnt, d_starts, nt, d_span, d_base, stage.p, d_out));
     HIPCHK(ctx, hipStreamSynchronize(s));
+    return MRZ_OK;
+}
+
+// bytes [lo, lo + cnt) of one chunk
+int range_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, int where0, const mrz_arc_table &s1,
+                       int64_t s1_len, int cb, int64_t lo, int64_t cnt, uint8_t *d_out, mrz_archive_range_info &acc) {
+    return chunk_blocks(
+        ctx, cus, s1, cnt,
+        [&](int64_t *d_org, mrz_range_info *ri) {
+            return mrz_runzip_origins(ctx, s0, s0_len, s1_len, where0, cb, lo, cnt, d_org, MRZ_MEM_DEVICE, ri);
+        },
+        d_out, acc);
+}
+
+// The parts of one chunk that a list of ranges asks for, to d_out + part.out_at each (device memory): the parts are
+// resolved flat, in list order, by ONE mrz_runzip_origins_multi (one parse of stream 0), gathered flat by the same span
+// and gather kernels, and -- unless they follow each other in the output anyway, where they are gathered in place --
+// moved to their places by one mrz_copy_device_batch.
+int ranges_chunk_blocks(mrz_ctx *ctx, int cus, const void *s0, int64_t s0_len, int where0, const mrz_arc_table &s1,
+                        int64_t s1_len, int cb, const std::vector<mrz_arc_part> &parts, uint8_t *d_out,
+                        mrz_archive_range_info &acc) {
+    std::vector<mrz_byte_range> rl(parts.size());
+    int64_t cnt = 0;
+    for (size_t k = 0; k < parts.size(); k++) {
+        rl[k] = mrz_byte_range{ parts[k].lo, parts[k].cnt };
+        cnt += parts[k].cnt;
+    }
+    const bool in_place = mrz_arc_ranges::contiguous(parts);
+    DeviceBuf flat;
+    if (!in_place && hipMalloc((void **)&flat.p, (size_t)cnt) != hipSuccess) return MRZ_E_NOMEM;
+    int rc = chunk_blocks(
+        ctx, cus, s1, cnt,
+        [&](int64_t *d_org, mrz_range_info *ri) {
+            return mrz_runzip_origins_multi(ctx, s0, s0_len, s1_len, where0, cb, rl.data(), (int64_t)rl.size(), d_org,
+                                            MRZ_MEM_DEVICE, ri);
+        },
+        in_place ? d_out + parts[0].out_at : flat.p, acc);
+    if (rc || in_place) return rc;
+    std::vector<const void *> src(parts.size());
+    std::vector<void *> dst(parts.size());
+    std::vector<int64_t> lens(parts.size());
+    int64_t at = 0;
+    for (size_t k = 0; k < parts.size(); k++) {
+        src[k] = flat.p + at;
+        dst[k] = d_out + parts[k].out_at;
+        lens[k] = parts[k].cnt;
+        at += parts[k].cnt;
+    }
+    return mrz_copy_device_batch(ctx, src.data(), dst.data(), lens.data(), (int64_t)parts.size());
+}
+
+// mrz_runzip_buffer_ranges: runzip_buffer_range_ex_impl with mrz_arc_ranges in place of mrz_arc_range.  `shared`: a
+// context of the caller's to work on (mrz_ar_extract_mrz makes three calls on one); NULL: one is opened on first need.
+int runzip_buffer_ranges_impl(mrz_ctx *shared, int device, const void *mrz_v, int64_t n, const mrz_byte_range *ranges,
+                              int64_t n_ranges, void *out, int out_where, int64_t *file_len,
+                              mrz_archive_range_info &acc) {
+    if (!mrz_v || n_ranges < 0 || (n_ranges > 0 && !ranges) || (out_where != MRZ_MEM_HOST && out_where != MRZ_MEM_DEVICE))
+        return MRZ_E_ARG;
+    const uint8_t *mrz = (const uint8_t *)mrz_v;
+    mrz_arc_header h;
+    int rc = mrz_arc_read_header(mrz, n, &h);
+    if (rc) return rc;
+    mrz_arc_ranges rg;
+    rc = rg.begin(h, ranges, n_ranges, file_len);
+    if (rc || (rg.size_known && !rg.sum)) return rc;
+    if (!out && rg.sum > 0) {
+        if (rg.size_known) return MRZ_E_ARG;
+        rg.bad = true;
+    }
+    CtxGuard g;
+    mrz_ctx *ctx = shared;
+    int cus = 0;
+    auto open_ctx = [&]() {  // on first need: an archive may be walked without any device work
+        if (!cus) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (ctx) return (int)MRZ_OK;
+        const int r = mrz_open(&g.ctx, device, 7, 0);
+        ctx = g.ctx;
+        return r;
+    };
+    DeviceBuf scratch;  // the packed ranges, when `out` is host memory
+    uint8_t *d_out = out_where == MRZ_MEM_DEVICE ? (uint8_t *)out : nullptr;
+    mrz_arc_cursor cur{ mrz, n, h.first_chunk, MRZ_ARC_NONE_LZ4 };
+    mrz_arc_chunk c;
+    std::vector<uint8_t> s0;
+    std::vector<mrz_arc_part> parts;
+    do {
+        rc = cur.next(c);
+        if (rc) return rc;
+        // stream 0 and the chunk's length: as runzip_buffer_range_ex_impl has them
+        int64_t s0_lz4 = 0;
+        for (const mrz_arc_block &b : c.blocks[0])
+            if (b.ctype == MRZ_CTYPE_LZ4) s0_lz4 += b.u_len;
+        const bool s0_on_device = s0_lz4 > 0;
+        DeviceStreams ds;
+        int64_t chunk_len = 0;
+        if (s0_on_device) {
+            if (c.blocks[0].size() > 0x7fffffffu) return MRZ_E_UNSUPPORTED;
+            rc = open_ctx();
+            if (rc) return rc;
+            rc = build_device_streams(ctx, c, 1, ds);
+            if (rc) return rc;
+            acc.s0_lz4_bytes += s0_lz4;
+            mrz_range_info ri;
+            rc = mrz_runzip_origins(ctx, ds.s0, c.stream_len[0], c.stream_len[1], MRZ_MEM_DEVICE, c.cb, 0, 0, nullptr,
+                                    MRZ_MEM_DEVICE, &ri);
+            if (rc == MRZ_E_ARG) rc = MRZ_E_CORRUPT;  // too short to hold a terminator
+            if (rc) return rc;
+            chunk_len = ri.chunk_len;
+        } else {
+            c.gather(0, s0);
+            if (!mrz_arc_records_out_len(s0.data(), (int64_t)s0.size(), c.cb, &chunk_len)) return MRZ_E_CORRUPT;
+        }
+        if (rg.clip(chunk_len, parts)) {
+            rc = open_ctx();
+            if (rc) return rc;
+            if (!d_out) {
+                if (hipMalloc((void **)&scratch.p, (size_t)rg.sum) != hipSuccess) return MRZ_E_NOMEM;
+                d_out = scratch.p;
+            }
+            mrz_arc_table s1;
+            s1.set(std::move(c.blocks[1]));
+            rc = ranges_chunk_blocks(ctx, cus, s0_on_device ? (const void *)ds.s0 : (const void *)s0.data(),
+                                     s0_on_device ? c.stream_len[0] : (int64_t)s0.size(),
+                                     s0_on_device ? MRZ_MEM_DEVICE : MRZ_MEM_HOST, s1, c.stream_len[1], c.cb, parts, d_out,
+                                     acc);
+            if (rc) return rc;
+        }
+        rg.total += chunk_len;
+    } while (!rg.covered() && !c.eof);
+    rc = rg.finish(file_len);
+    if (rc || !rg.sum) return rc;
+    if (!out) return MRZ_E_ARG;
+    if (scratch.p && hipMemcpy(out, scratch.p, (size_t)rg.sum, hipMemcpyDeviceToHost) != hipSuccess) return MRZ_E_HIP;
     return MRZ_OK;
 }
 
@@ -429,6 +565,24 @@ extern "C" int mrz_runzip_buffer(int device, const void *mrz, int64_t n, void **
 extern "C" int mrz_runzip_buffer_range(int device, const void *mrz, int64_t n, int64_t first, int64_t count,
                                        void *out_host, int64_t *file_len) {
     return no_throw([&] { return runzip_buffer_range_impl(device, mrz, n, first, count, out_host, file_len); });
+}
+
+int mrz_runzip_buffer_ranges_on(mrz_ctx *ctx, int device, const void *mrz, int64_t n, const mrz_byte_range *ranges,
+                                int64_t n_ranges, void *out, int out_where, int64_t *file_len,
+                                mrz_archive_range_info *info) {
+    mrz_archive_range_info acc;
+    memset(&acc, 0, sizeof(acc));
+    const int rc = no_throw([&] {
+        return runzip_buffer_ranges_impl(ctx, device, mrz, n, ranges, n_ranges, out, out_where, file_len, acc);
+    });
+    if (info) *info = acc;
+    return rc;
+}
+
+extern "C" int mrz_runzip_buffer_ranges(int device, const void *mrz, int64_t n, const mrz_byte_range *ranges,
+                                        int64_t n_ranges, void *out, int out_where, int64_t *file_len,
+                                        mrz_archive_range_info *info) {
+    return mrz_runzip_buffer_ranges_on(nullptr, device, mrz, n, ranges, n_ranges, out, out_where, file_len, info);
 }
 
 extern "C" int mrz_runzip_buffer_range_ex(int device, const void *mrz, int64_t n, int64_t first, int64_t count, void *out,
